@@ -13,6 +13,11 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline figure needs. `--dump-outputs DIR`
+additionally writes the last timed step's factors/lambda/fit as .npy files
+(inputs are seeded, so two builds can be compared output for output);
+`--full` adds the measurements beyond the headline (per-phase breakdown).
+
 Default experiment = BASELINE.json config 4: Amazon-Reviews-shaped
 (4.8M x 1.8M x 1.8M, 1.74B nnz) rank-16 f64 CPD-ALS, medium-grained
 nmodes-D grid over the N GPUs at FIXED global nnz — STRONG scaling, so the
@@ -70,6 +75,36 @@ def synth_box_shard(dec, nnz, seed, dtype, device, dist="uniform"):
     return sp.SpTensor(inds, vals, local_dims).to(device)
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all dumped arrays together stay under 64 MB
+
+
+def dump_outputs(outdir, st, rank, world):
+    """Write what the last timed step produced — the factor matrices, lambda
+    and the fit, i.e. the Kruskal result a caller of the ALS step receives —
+    as <outdir>/<name>.npy. A factor larger than its share of the budget is
+    written as a fixed, seeded sample of its rows (sorted row order), so two
+    builds run with the same arguments dump the same rows."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    per_factor = DUMP_BUDGET_BYTES // len(st.factors)
+    for m, fac in enumerate(st.factors):
+        nrows, ncols = fac.shape
+        cap = max(1, per_factor // (ncols * fac.element_size()))
+        if nrows > cap:
+            rows = np.sort(np.random.default_rng(0xD0 + m).choice(
+                nrows, size=cap, replace=False))
+            fac = fac.index_select(
+                0, torch.from_numpy(rows).to(fac.device))
+        np.save(os.path.join(outdir, f"factor{m}{sfx}.npy"),
+                fac.detach().cpu().numpy())
+    np.save(os.path.join(outdir, f"lambda{sfx}.npy"),
+            st.lam.detach().cpu().numpy())
+    if rank == 0:
+        np.save(os.path.join(outdir, "fit.npy"),
+                np.array([st.fit], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -112,6 +147,15 @@ def main():
                          "(strong scaling; the BASELINE configs 4/5 shape); "
                          "coarse = 1D layers on the longest mode, per-rank "
                          "work fixed (weak scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factors, lambda "
+                         "and fit of the last timed step as DIR/<name>.npy "
+                         "(large factors as a fixed seeded row sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure "
+                         "(today: the --profile per-phase breakdown); a "
+                         "plain run only sets up, warms up, times the steps "
+                         "and prints the result line")
     args = ap.parse_args()
 
     if args.deterministic:
@@ -230,7 +274,11 @@ def main():
     if runner is not None:
         runner.finalize(st.norm_x)
 
-    if args.profile:
+    # before any further step touches the state
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, st, rank, world)
+
+    if args.profile or args.full:
         from splatt_amd.utils.timers import TimerRegistry
         reg = TimerRegistry(sync_device=device.type == "cuda")
         for _ in range(3):

@@ -9,6 +9,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
+# The gloo/CPU launches below start more ranks than a test box has GPUs;
+# hide any GPU from the children so bench.py's default device resolves to
+# the host path on every machine (an out-of-range index ends the list).
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1", "CUDA_VISIBLE_DEVICES": "-1"}
+
 
 @pytest.mark.timeout(420)
 @pytest.mark.parametrize("decomp", ["coarse", "medium"])
@@ -62,7 +67,7 @@ def test_bench_driver_argv_world8(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1",
                SPLATT_BENCH_CONFIG="small",
                SPLATT_FORCE_RS_PRIMS="1",
-               SPLATT_COMM_CHUNK_MIN_MB="0")
+               SPLATT_COMM_CHUNK_MIN_MB="0", **NO_GPU)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--standalone",
          "--nnodes=1", "--nproc-per-node", "8", "--local-addr", "127.0.0.1",
@@ -85,7 +90,7 @@ def test_bench_driver_argv_world8_4mode(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1",
                SPLATT_BENCH_CONFIG="small4",
                SPLATT_FORCE_RS_PRIMS="1",
-               SPLATT_COMM_CHUNK_MIN_MB="0")
+               SPLATT_COMM_CHUNK_MIN_MB="0", **NO_GPU)
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--standalone",
          "--nnodes=1", "--nproc-per-node", "8", "--local-addr", "127.0.0.1",

@@ -174,6 +174,89 @@ def test_bench_contract_json(tmp_path):
     assert j["higher_is_better"] is True
 
 
+def _run_bench(root, *extra):
+    import json
+    import subprocess
+    import sys as _sys
+    r = subprocess.run(
+        [_sys.executable, "bench.py", "--device", "cpu", "--config", "small",
+         "--steps", "2", "--warmup", "1", *extra],
+        capture_output=True, text=True, cwd=root, timeout=300)
+    assert r.returncode == 0, r.stderr[-500:]
+    lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), r.stderr
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's Kruskal result as float
+    .npy files, identical inputs give matching outputs run to run, and the
+    per-phase breakdown only appears under --full."""
+    import os
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    da, db = tmp_path / "a", tmp_path / "b"
+    ja, err_a = _run_bench(root, "--dump-outputs", str(da))
+    jb, err_b = _run_bench(root, "--dump-outputs", str(db), "--full")
+    assert "Timing information" not in err_a
+    assert "Timing information" in err_b
+    assert ja["steps"] == jb["steps"] == 2 and ja["ms_per_step"] > 0
+    names = sorted(p.name for p in da.iterdir())
+    assert names == ["factor0.npy", "factor1.npy", "factor2.npy", "fit.npy",
+                     "lambda.npy"]
+    assert names == sorted(p.name for p in db.iterdir())
+    dims = ja["config"]["dims"]
+    for n in names:
+        a, b = np.load(da / n), np.load(db / n)
+        assert a.dtype in (np.float32, np.float64)
+        assert np.isfinite(a).all()
+        # --full's extra steps must not leak into the dumped state
+        np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-12)
+    for m, d in enumerate(dims):
+        assert np.load(da / f"factor{m}.npy").shape == (d, 16)
+    assert np.load(da / "lambda.npy").shape == (16,)
+    assert abs(float(np.load(da / "fit.npy")[0]) - ja["config"]["fit"]) < 1e-6
+
+
+def test_bench_dump_outputs_samples_large_factor(tmp_path, monkeypatch):
+    """A factor over its share of the 64 MB budget is written as a fixed,
+    seeded, sorted row sample."""
+    import importlib.util
+    import os
+    import types
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # importing bench.py sets this default; undo it after the test
+    monkeypatch.setenv("PYTORCH_HIP_ALLOC_CONF", os.environ.get(
+        "PYTORCH_HIP_ALLOC_CONF", "expandable_segments:True"))
+    spec = importlib.util.spec_from_file_location(
+        "_bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    big = torch.rand(1_200_000, 16, generator=g, dtype=torch.float64)
+    st = types.SimpleNamespace(
+        factors=[big, big[:100].clone()],
+        lam=torch.ones(16, dtype=torch.float64), fit=0.25)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), st, 0, 1)
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= 64 * 1000 * 1000
+    f0 = np.load(tmp_path / "a" / "factor0.npy")
+    assert f0.dtype == np.float64 and f0.shape[1] == 16
+    assert 100_000 < f0.shape[0] < big.shape[0]
+    assert np.array_equal(f0, np.load(tmp_path / "b" / "factor0.npy"))
+    # rows are real rows of the factor, in ascending row order
+    col = big[:, 0].numpy()
+    order = np.argsort(col)
+    idx = order[np.searchsorted(col[order], f0[:, 0])]
+    assert np.array_equal(big.numpy()[idx], f0)
+    assert (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "factor1.npy"),
+                          big[:100].numpy())
+    assert float(np.load(tmp_path / "a" / "fit.npy")[0]) == 0.25
+
+
 def test_cli_reorder_partfile(tmp_path, small3):
     """graph/hgraph reorder driven by an external partition file."""
     tns = str(tmp_path / "t.tns")

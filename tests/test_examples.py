@@ -18,7 +18,10 @@ def test_quickstart_runs():
 
 @pytest.mark.timeout(420)
 def test_distributed_example_runs():
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    # two ranks: run the gloo/CPU path wherever there are fewer GPUs than
+    # ranks (an out-of-range index hides every device from the children)
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1",
+               HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--standalone",
          "--nnodes=1", "--nproc-per-node", "2", "--local-addr", "127.0.0.1",
