@@ -9,6 +9,7 @@
 // Capability parity: reference mat_aTa (src/matrix.c:414-455).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "mfma_acc.hpp"
 
 namespace {
 
@@ -65,27 +66,8 @@ gram_kern(const V * __restrict__ A, int64_t n, int F, int64_t rows_per_blk,
 // chunk^T * chunk directly. Each wave folds its row range 4 rows per
 // MFMA into (F/16)^2 16x16 accumulator tiles (upper-triangular block
 // pairs only; the mirror is written in the epilogue).
-template <typename V> struct MfmaAcc;
-template <> struct MfmaAcc<double> {
-  using type = __attribute__((ext_vector_type(4))) double;
-  static __device__ __forceinline__ type mfma(double a, double b, type c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // f64 16x16x4 C/D row map (probed on gfx950): row = lane/16 + 4*reg
-  static __device__ __forceinline__ int crow(int lane, int i) {
-    return (lane >> 4) + 4 * i;
-  }
-};
-template <> struct MfmaAcc<float> {
-  using type = __attribute__((ext_vector_type(4))) float;
-  static __device__ __forceinline__ type mfma(float a, float b, type c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  // f32 16x16x4 uses the standard map: row = (lane/16)*4 + reg
-  static __device__ __forceinline__ int crow(int lane, int i) {
-    return (lane >> 4) * 4 + i;
-  }
-};
+// (MfmaAcc — the builtin + C/D row map per value type — lives in
+// mfma_acc.hpp, shared with complete_als.hip.)
 
 template <typename V, int F>
 __global__ void __launch_bounds__(256)

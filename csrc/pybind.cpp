@@ -762,7 +762,138 @@ static void py_gpu_mttkrp3(int which, Tensor fptr0, py::object fids0, Tensor fpt
     gpu_mttkrp3_t<double>(which, fptr0, fids0, fptr1, fids1, fids2, vals, Ma, Mb, out, stream);
 }
 
+// ------------------------------------------- tensor completion (f64 only)
+extern "C" {
+// csrc/hip/complete_als.hip; nonzero return = hipError_t of the launch
+int64_t splatt_hip_complete_slot_elems(int);
+const char * splatt_hip_complete_errstr(int);
+int splatt_hip_complete_segments_f64(
+    const int32_t* const*, const double* const*, int, const double*,
+    const int64_t*, const int32_t*, const int32_t*, const int32_t*, int64_t,
+    int64_t, int64_t, int, double, double*, double*, void*);
+int splatt_hip_complete_reduce_f64(
+    const double*, const int32_t*, const int64_t*, int64_t, int64_t, int64_t,
+    int, double, double*, void*);
+int splatt_hip_kruskal_predict_f64(
+    const int64_t* const*, const double* const*, int, const double*, int64_t,
+    int, double*, void*);
+}
+
+static void check_dev(const Tensor & t, torch::ScalarType ty,
+                      const char * name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
+  TORCH_CHECK(t.scalar_type() == ty, name, " has dtype ", t.scalar_type(),
+              ", expected ", ty);
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+// One batch of the row-wise completion update for a root-sorted stream:
+// segments [seg0, seg0+nseg) accumulate (and solve single-segment rows),
+// then multi-segment rows [m0, m0+nm) are folded from `ws` and solved.
+// Slots slot0..slot0+nslots-1 live in `ws` during this batch.
+static void py_gpu_complete_update(
+    std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
+    Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
+    int64_t seg0, int64_t nseg, Tensor mrow, Tensor mslot, int64_t m0,
+    int64_t nm, int64_t slot0, int64_t nslots, double reg, Tensor ws,
+    Tensor out, int64_t stream) {
+  const int nother = (int)idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "completion supports 3..8 modes");
+  TORCH_CHECK((int)mats.size() == nother);
+  TORCH_CHECK(reg > 0.0, "reg must be > 0");
+  check_dev(vals, torch::kFloat64, "vals");
+  check_dev(out, torch::kFloat64, "out");
+  check_dev(ws, torch::kFloat64, "ws");
+  check_dev(seg_start, torch::kInt64, "seg_start");
+  check_dev(seg_len, torch::kInt32, "seg_len");
+  check_dev(seg_row, torch::kInt32, "seg_row");
+  check_dev(seg_slot, torch::kInt32, "seg_slot");
+  check_dev(mrow, torch::kInt32, "mrow");
+  check_dev(mslot, torch::kInt64, "mslot");
+  TORCH_CHECK(out.dim() == 2, "out must be [rows, rank]");
+  const int F = (int)out.size(1);
+  TORCH_CHECK(F >= 1 && F <= 64, "completion supports rank 1..64, got ", F);
+  const int64_t nnz = vals.numel();
+  const int32_t * ip[8] = {};
+  const double * mp[8] = {};
+  for (int t = 0; t < nother; ++t) {
+    check_dev(idx[t], torch::kInt32, "idx");
+    check_dev(mats[t], torch::kFloat64, "factor");
+    TORCH_CHECK(idx[t].numel() == nnz, "index stream length != nnz");
+    TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) == F,
+                "factor rank mismatch");
+    ip[t] = idx[t].data_ptr<int32_t>();
+    mp[t] = mats[t].data_ptr<double>();
+  }
+  TORCH_CHECK(seg_len.numel() == seg_start.numel()
+              && seg_row.numel() == seg_start.numel()
+              && seg_slot.numel() == seg_start.numel());
+  TORCH_CHECK(seg0 >= 0 && nseg >= 0 && seg0 + nseg <= seg_start.numel(),
+              "segment range out of bounds");
+  TORCH_CHECK(m0 >= 0 && nm >= 0 && m0 + nm <= mrow.numel()
+              && mslot.numel() == mrow.numel() + 1,
+              "multi-segment row range out of bounds");
+  TORCH_CHECK(nslots >= 0 && slot0 >= 0
+              && ws.numel() >= nslots * splatt_hip_complete_slot_elems(F),
+              "completion workspace too small");
+  int rc = splatt_hip_complete_segments_f64(
+      ip, mp, nother, vals.data_ptr<double>(), seg_start.data_ptr<int64_t>(),
+      seg_len.data_ptr<int32_t>(), seg_row.data_ptr<int32_t>(),
+      seg_slot.data_ptr<int32_t>(), seg0, nseg, slot0, F, reg,
+      ws.data_ptr<double>(), out.data_ptr<double>(), (void*)stream);
+  TORCH_CHECK(rc == 0, "completion segment kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+  rc = splatt_hip_complete_reduce_f64(
+      ws.data_ptr<double>(), mrow.data_ptr<int32_t>(),
+      mslot.data_ptr<int64_t>(), m0, nm, slot0, F, reg,
+      out.data_ptr<double>(), (void*)stream);
+  TORCH_CHECK(rc == 0, "completion reduce kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+}
+
+// out[p] = sum_f lam_f prod_t mats[t][inds[t,p], f]; inds is [nmodes, n]
+static void py_gpu_kruskal_predict(Tensor inds, std::vector<Tensor> mats,
+                                   py::object lam, Tensor out,
+                                   int64_t stream) {
+  check_dev(inds, torch::kInt64, "inds");
+  check_dev(out, torch::kFloat64, "out");
+  TORCH_CHECK(inds.dim() == 2, "inds must be [nmodes, n]");
+  const int nm = (int)inds.size(0);
+  const int64_t n = inds.size(1);
+  TORCH_CHECK(nm >= 1 && nm <= 8 && (int)mats.size() == nm,
+              "need one factor per mode (1..8 modes)");
+  TORCH_CHECK(out.numel() == n, "out length != number of coordinates");
+  const int F = (int)mats[0].size(1);
+  const int64_t * ip[8] = {};
+  const double * mp[8] = {};
+  for (int t = 0; t < nm; ++t) {
+    check_dev(mats[t], torch::kFloat64, "factor");
+    TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) == F,
+                "factor rank mismatch");
+    ip[t] = inds.data_ptr<int64_t>() + (int64_t)t * n;
+    mp[t] = mats[t].data_ptr<double>();
+  }
+  const double * lp = nullptr;
+  Tensor lt;
+  if (!lam.is_none()) {
+    lt = lam.cast<Tensor>();
+    check_dev(lt, torch::kFloat64, "lam");
+    TORCH_CHECK(lt.numel() == F, "lam length != rank");
+    lp = lt.data_ptr<double>();
+  }
+  const int rc = splatt_hip_kruskal_predict_f64(
+      ip, mp, nm, lp, n, F, out.data_ptr<double>(), (void*)stream);
+  TORCH_CHECK(rc == 0, "kruskal_predict kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gpu_complete_update", &py_gpu_complete_update,
+        "row-wise completion update: one batch of segments + row solves");
+  m.def("complete_slot_elems", &splatt_hip_complete_slot_elems,
+        "workspace doubles per segment slot at a rank");
+  m.def("gpu_kruskal_predict", &py_gpu_kruskal_predict,
+        "Kruskal model values at COO coordinates");
   m.def("tensor_load", &py_tensor_load, "load .tns/.bin tensor");
   m.def("tns_write", &py_tns_write);
   m.def("bin_write", &py_bin_write);

@@ -30,9 +30,14 @@ def build_hip_objects():
     objdir.mkdir(parents=True, exist_ok=True)
     objs = []
     rebuilt = False
+    # headers shared between kernel files (mfma_acc.hpp, store_types.hpp)
+    hdr_mtime = max((h.stat().st_mtime
+                     for h in (ROOT / "csrc" / "hip").glob("*.hpp")),
+                    default=0.0)
     for src in HIP_SOURCES:
         obj = objdir / (src.stem + ".o")
-        if not obj.exists() or obj.stat().st_mtime < src.stat().st_mtime:
+        if (not obj.exists()
+                or obj.stat().st_mtime < max(src.stat().st_mtime, hdr_mtime)):
             cmd = [
                 HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17",
                 "-fPIC", "-munsafe-fp-atomics", "-c", str(src), "-o", str(obj),

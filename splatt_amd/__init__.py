@@ -16,6 +16,8 @@ from splatt_amd.mttkrp import mttkrp, mttkrp_stream
 from splatt_amd.cpd import CpdOptions, Kruskal, cpd_als, cpd_als_cpu_native, seeded_init
 from splatt_amd.kruskal import (kruskal_fit, kruskal_innerprod, kruskal_norm,
                                 kruskal_to_dense)
+from splatt_amd.completion import (CompleteOptions, Completion, complete_als,
+                                   complete_update, kruskal_predict, rmse)
 
 load = SpTensor.load
 
@@ -24,4 +26,6 @@ __all__ = [
     "order_modes", "mttkrp", "mttkrp_stream", "CpdOptions", "Kruskal",
     "cpd_als", "cpd_als_cpu_native", "seeded_init", "load",
     "kruskal_fit", "kruskal_innerprod", "kruskal_norm", "kruskal_to_dense",
+    "CompleteOptions", "Completion", "complete_als", "complete_update",
+    "kruskal_predict", "rmse",
 ]

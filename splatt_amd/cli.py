@@ -28,6 +28,57 @@ def _load(args) -> "sp.SpTensor":
     return t
 
 
+def _write_matrix(path: str, A: torch.Tensor) -> None:
+    """Dense matrix as text, one row per line (the `modeN.mat` format)."""
+    with open(path, "w") as fh:
+        for row in A.cpu().tolist():
+            fh.write(" ".join(f"{x:.17g}" for x in row) + "\n")
+
+
+def cmd_complete(args) -> int:
+    """`splatt complete`: regularised ALS over the observed entries, with
+    held-out validation / test RMSE."""
+    import os
+    if args.dtype != "f64":
+        raise ValueError("complete supports float64 tensors only "
+                         "(--dtype f64)")
+    t = _load(args)
+    print(stats_tt(t, args.tensor))
+    dev = args.device
+    if dev == "auto":
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+    val = sp.SpTensor.load(args.validate) if args.validate else None
+    test = sp.SpTensor.load(args.test) if args.test else None
+    for name, h in (("--validate", val), ("--test", test)):
+        if h is not None and (h.nmodes != t.nmodes or any(
+                hd > td for hd, td in zip(h.dims, t.dims))):
+            raise ValueError(f"{name} tensor {h.dims} does not fit inside "
+                             f"the training tensor's dims {t.dims}")
+    opts = sp.CompleteOptions(max_iters=args.its, regularize=args.reg,
+                              tolerance=args.tol, seed=args.seed,
+                              verbose=True)
+    with TIMERS.time("COMPLETE"):
+        cs = sp.csf_alloc(t.to(dev), "all")
+        print(stats_csf(cs))
+        r = sp.complete_als(cs, args.rank, opts,
+                            validate=val.to(dev) if val is not None else None)
+    line = (f"Final objective: {r.objective_trace[-1]:.6e}  train RMSE: "
+            f"{r.rmse_train_trace[-1]:.5f}  (iterations: {r.niters}")
+    if val is not None:
+        line += (f"; best validation RMSE {r.rmse_val_trace[r.best_iter]:.5f}"
+                 f" at iteration {r.best_iter + 1}")
+    print(line + ")")
+    if test is not None:
+        print(f"Test RMSE: {sp.rmse(r.factors, test.to(dev)):.5f}")
+    if args.write is not None:
+        os.makedirs(args.write, exist_ok=True)
+        for m, f in enumerate(r.factors):
+            _write_matrix(os.path.join(args.write, f"mode{m + 1}.mat"), f)
+        print(f"wrote {len(r.factors)} factor matrices to {args.write}")
+    print(TIMERS.report())
+    return 0
+
+
 def cmd_cpd(args) -> int:
     import os
     if getattr(args, "csf", None) is None:
@@ -74,9 +125,7 @@ def cmd_cpd(args) -> int:
     print(f"Final fit: {k.fit:.5f}  (iterations: {k.niters})")
     if not args.nowrite:
         for m, f in enumerate(k.factors):
-            with open(f"mode{m + 1}.mat", "w") as fh:
-                for row in f.cpu().tolist():
-                    fh.write(" ".join(f"{x:.17g}" for x in row) + "\n")
+            _write_matrix(f"mode{m + 1}.mat", f)
         with open("lambda.mat", "w") as fh:
             for x in k.lam.cpu().tolist():
                 fh.write(f"{x:.17g}\n")
@@ -253,6 +302,27 @@ def main(argv=None) -> int:
                         "kernels, >=80%% throughput; implies --csf all)")
     p.add_argument("-v", "--verbose", action="count", default=0)
     p.set_defaults(fn=cmd_cpd)
+
+    p = sub.add_parser("complete",
+                       help="tensor completion: ALS over observed entries")
+    _add_common(p)
+    p.add_argument("--validate", help="held-out tensor: early stopping and "
+                                      "best-iteration selection")
+    p.add_argument("--test", help="held-out tensor: final RMSE report")
+    p.add_argument("-r", "--rank", type=int, default=10)
+    p.add_argument("-i", "--iters", "--its", dest="its", type=int,
+                   default=50)
+    p.add_argument("--reg", type=float, default=1e-2,
+                   help="ridge weight on every factor (must be > 0)")
+    p.add_argument("-t", "--tol", type=float, default=1e-4,
+                   help="stop when the relative improvement of the "
+                        "validation RMSE (else the objective) drops below")
+    p.add_argument("--seed", type=int, default=0x5EED5EED)
+    p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    p.add_argument("--write", nargs="?", const=".", default=None,
+                   metavar="DIR",
+                   help="write modeN.mat factor files (into DIR, default .)")
+    p.set_defaults(fn=cmd_complete)
 
     p = sub.add_parser("check", help="find/repair duplicates + empty slices")
     _add_common(p)
