@@ -209,14 +209,307 @@ mttkrp_flat2_kern(const int32_t * __restrict__ key,
   atomic_add_g(&out[(int64_t)cur * F + c], acc);
 }
 
-// storage-typed launcher for the v2 kernel (the default spec path):
-// reduced-precision factor STORE for non-staged HBM-bound dispatches
-inline int64_t pick_span_decl(int64_t nnz);
+// --------------------------------- full-line staged spec kernel (v7)
+// v2's F-element stream window is 64 B of an int32 stream at F=16 (32 B at
+// F=8): two (four) consecutive windows touch the same 128-B line, the
+// loads are non-temporal and a batch of random row gathers sits between
+// them, so the line is fetched from HBM again on every touch
+// (profiles/amazon_stream_lines.md). v7 stages a fixed window of W=32
+// nonzeros whatever F is, so every stream load instruction of a column
+// group covers whole 128-B lines and every line is loaded by exactly one
+// instruction:
+//   int32 streams  lane slot s loads EPL = 32/F consecutive elements
+//                  (4/8/16-B load); element e of the window lives in lane
+//                  gbase + e/EPL, component e%EPL
+//   vals (f64)     NVL = 2 loads of 128 B each for F <= 16 (element e:
+//                  load e/CH, lane gbase + (e%CH)/VPL, component e%VPL);
+//                  f32 vals follow the int32 layout
+// Windows are aligned to 32 elements of the underlying allocation: the
+// launcher passes `phase` (elements from the preceding 128-B boundary to
+// the first element) and rounds span so sub-spans start on window
+// boundaries; the partial windows at the two ends of a launch take a
+// scalar per-element path. Gather batch (8) and the fold order within a
+// sub-span are those of v2.
+//
+// RP = true replaces the key stream by row pointers (root output of a
+// key-sorted stream): a sub-span binary-searches its first row once, keeps
+// the position `next` at which the row ends and, one boundary ahead,
+// `next2`; when the walk reaches `next` it flushes, advances (skipping
+// empty rows, which therefore get no atomic) and loads the boundary after
+// the new `next` — a load nothing waits on before the following run change.
+template <typename T, int N>
+__device__ __forceinline__ void ldnt_vec(const T * p, T (&r)[N]) {
+  if constexpr (N == 1) {
+    r[0] = ldnt(p);
+  } else {
+    using VT = T __attribute__((ext_vector_type(N)));
+    const VT v = __builtin_nontemporal_load(reinterpret_cast<const VT *>(p));
+    #pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = v[i];
+  }
+}
+
+template <typename V, int F, int NOTHER, typename S, bool RP>
+__global__ void __launch_bounds__(256)
+mttkrp_flat7_kern(const int32_t * __restrict__ key,
+                  const int64_t * __restrict__ rowptr, int64_t nrows,
+                  int64_t goff,
+                  const int32_t * __restrict__ i0,
+                  const int32_t * __restrict__ i1,
+                  const int32_t * __restrict__ i2,
+                  const int32_t * __restrict__ i3,
+                  const S * __restrict__ m0, const S * __restrict__ m1,
+                  const S * __restrict__ m2, const S * __restrict__ m3,
+                  const V * __restrict__ vals, int64_t nnz, int64_t span,
+                  int phase, V * __restrict__ out) {
+  constexpr int R = WAVE / F;
+  constexpr int W = 32;                          // stream window (nnz)
+  constexpr int EPL = (F >= W) ? 1 : W / F;      // int32 elements per lane
+  constexpr int VPL = (sizeof(V) == 8 && EPL > 1) ? EPL / 2 : EPL;
+  constexpr int NVL = EPL / VPL;                 // vals loads per window
+  constexpr int CH = W / NVL;                    // elements per vals load
+  constexpr int GB = 8;                          // gather sub-batch
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
+                      + (threadIdx.x / WAVE);
+  const int c = lane % F;
+  const int g = lane / F;
+  const int gbase = g * F;
+  const int slot = c & (W / EPL - 1);            // F=64: lanes 32.. mirror
+  // positions q are relative to the 128-B-aligned base `phase` elements
+  // before the first nonzero; the launch covers [phase, phase + nnz)
+  const int64_t gs = span / R;                   // multiple of W
+  const int64_t q0 = wid * span + g * gs;
+  const int64_t a = q0 > phase ? q0 : (int64_t)phase;
+  const int64_t b = min64(q0 + gs, phase + nnz);
+  if (a >= b) return;
+
+  int32_t cur;
+  int64_t next = 0, next2 = 0;
+  int nrel = 0;             // `next` relative to the window, clamped to W
+  int64_t pwg = 0;          // global stream position of the window start
+  if constexpr (RP) {
+    const int64_t P = a - phase + goff;
+    int64_t l = 0, h = nrows;          // rowptr[l] <= P < rowptr[h]
+    while (h - l > 1) {
+      const int64_t mid = (l + h) >> 1;
+      if (rowptr[mid] <= P) l = mid; else h = mid;
+    }
+    cur = (int32_t)l;
+    next = rowptr[l + 1];
+    next2 = rowptr[min64(l + 2, nrows)];
+  } else {
+    cur = key[a - phase];
+  }
+  V acc = (V)0;
+
+  auto fold = [&](int e, int32_t k, V x) {
+    if constexpr (RP) {
+      if (e >= nrel) {
+        atomic_add_g(&out[(int64_t)cur * F + c], acc);
+        acc = (V)0;
+        const int64_t P = pwg + e;
+        do {                           // skips rows with no nonzeros
+          ++cur;
+          next = next2;
+          next2 = rowptr[min64((int64_t)cur + 2, nrows)];
+        } while (P >= next && (int64_t)cur + 1 < nrows);
+        nrel = (int)min64(next - pwg, (int64_t)W);
+      }
+    } else {
+      if (k != cur) {
+        atomic_add_g(&out[(int64_t)cur * F + c], acc);
+        acc = (V)0;
+        cur = k;
+      }
+    }
+    acc += x;
+  };
+
+  for (int64_t qb = a & ~(int64_t)(W - 1); qb < b; qb += W) {
+    const int64_t pw = qb - phase;     // stream index of window element 0
+    if constexpr (RP) {
+      pwg = pw + goff;
+      nrel = (int)min64(next - pwg, (int64_t)W);
+    }
+    if (qb >= a && qb + W <= b) {
+      const int64_t ps = pw + slot * EPL;
+      int32_t kreg[EPL], i0reg[EPL], i1reg[EPL], i2reg[EPL], i3reg[EPL];
+      V vreg[NVL][VPL];
+      if constexpr (!RP) ldnt_vec(key + ps, kreg);
+      ldnt_vec(i0 + ps, i0reg);
+      ldnt_vec(i1 + ps, i1reg);
+      if constexpr (NOTHER > 2) ldnt_vec(i2 + ps, i2reg);
+      if constexpr (NOTHER > 3) ldnt_vec(i3 + ps, i3reg);
+      #pragma unroll
+      for (int k = 0; k < NVL; ++k)
+        ldnt_vec(vals + pw + k * CH + slot * VPL, vreg[k]);
+      // batches of one vals chunk stay a rolled loop (the unrolled form
+      // hoists the next batch's gathers and costs a wave of occupancy);
+      // GB is a multiple of EPL and VPL, so register components stay
+      // compile-time and only the source lane depends on the batch
+      #pragma unroll
+      for (int k = 0; k < NVL; ++k) {
+        #pragma unroll 1
+        for (int h = 0; h < CH; h += GB) {
+          const int ub = k * CH + h;
+          V vv[GB];
+          S a0[GB], a1[GB], a2[GB], a3[GB];
+          #pragma unroll
+          for (int u = 0; u < GB; ++u) {
+            const int src = gbase + ub / EPL + u / EPL;
+            vv[u] = __shfl(vreg[k][u % VPL], gbase + h / VPL + u / VPL, WAVE);
+            const int32_t j0 = __shfl(i0reg[u % EPL], src, WAVE);
+            const int32_t j1 = __shfl(i1reg[u % EPL], src, WAVE);
+            a0[u] = m0[(int64_t)j0 * F + c];
+            a1[u] = m1[(int64_t)j1 * F + c];
+            if constexpr (NOTHER > 2) {
+              const int32_t j2 = __shfl(i2reg[u % EPL], src, WAVE);
+              a2[u] = m2[(int64_t)j2 * F + c];
+            }
+            if constexpr (NOTHER > 3) {
+              const int32_t j3 = __shfl(i3reg[u % EPL], src, WAVE);
+              a3[u] = m3[(int64_t)j3 * F + c];
+            }
+          }
+          #pragma unroll
+          for (int u = 0; u < GB; ++u) {
+            V x = vv[u] * to_compute(a0[u], (V)0) * to_compute(a1[u], (V)0);
+            if constexpr (NOTHER > 2) x *= to_compute(a2[u], (V)0);
+            if constexpr (NOTHER > 3) x *= to_compute(a3[u], (V)0);
+            // the key is redistributed at the fold, not with the batch:
+            // kreg is live anyway and the batch needs 8 registers less
+            int32_t k = 0;
+            if constexpr (!RP)
+              k = __shfl(kreg[u % EPL], gbase + ub / EPL + u / EPL, WAVE);
+            fold(ub + u, k, x);
+          }
+        }
+      }
+    } else {
+      // partial window at an end of the launch: one element at a time,
+      // every lane of the group reading the same stream words
+      const int e0 = (int)((a > qb ? a : qb) - qb);
+      const int e1 = (int)(min64(b, qb + W) - qb);
+      for (int e = e0; e < e1; ++e) {
+        const int64_t p = pw + e;
+        V x = ldnt(&vals[p])
+              * to_compute(m0[(int64_t)ldnt(&i0[p]) * F + c], (V)0)
+              * to_compute(m1[(int64_t)ldnt(&i1[p]) * F + c], (V)0);
+        if constexpr (NOTHER > 2)
+          x *= to_compute(m2[(int64_t)ldnt(&i2[p]) * F + c], (V)0);
+        if constexpr (NOTHER > 3)
+          x *= to_compute(m3[(int64_t)ldnt(&i3[p]) * F + c], (V)0);
+        int32_t k = 0;
+        if constexpr (!RP) k = ldnt(&key[p]);
+        fold(e, k, x);
+      }
+    }
+  }
+  atomic_add_g(&out[(int64_t)cur * F + c], acc);
+}
+
+inline int64_t pick_span(int64_t nnz) {
+  const char * e = getenv("SPLATT_SPAN_WAVES");   // tuning knob
+  const int64_t target_waves = e ? atoll(e) : 65536;
+  int64_t span = nnz / target_waves;
+  if (span < 256) span = 256;
+  if (span > 16384) span = 16384;
+  return span;
+}
+
+inline bool spec_ok(int F) {
+  return F == 4 || F == 8 || F == 16 || F == 32 || F == 64;
+}
+
+inline int pick_unroll() {
+  // A/B lever: 0 (default) = full-line staged v7 kernel (v2 at rank 4 or
+  // when the streams are not co-aligned); 1 = force v2; 2 = v2 with gather
+  // batch 4; 3 = v3; 5 = v4; 4/8/16 = v1 at that unroll
+  const char * e = getenv("SPLATT_MTTKRP_U");
+  const int u = e ? atoi(e) : 0;
+  return (u == 1 || u == 2 || u == 3 || u == 4 || u == 5 || u == 8
+          || u == 16) ? u : 0;
+}
+
+// Elements between the preceding 128-B line boundary of the int32 streams
+// and their first element, or -1 when the streams of this launch are not
+// co-aligned (some stream's line boundaries fall on other elements).
+template <typename V>
+inline int stream_phase(const int32_t * key, const int32_t * const idx[8],
+                        int nother, const V * vals) {
+  const int phase = (int)(((uintptr_t)idx[0] >> 2) & 31);
+  if (key && (int)(((uintptr_t)key >> 2) & 31) != phase) return -1;
+  for (int t = 1; t < nother; ++t)
+    if ((int)(((uintptr_t)idx[t] >> 2) & 31) != phase) return -1;
+  if ((uintptr_t)vals % sizeof(V)) return -1;
+  if ((int)(((uintptr_t)vals / sizeof(V)) & 31) != phase) return -1;
+  return phase;
+}
+
+// v7 launcher; rowptr != nullptr selects the row-pointer variant (key may
+// then be null). Returns false, launching nothing, when v7 does not apply:
+// rank outside 8/16/32/64, more than 4 other modes, an SPLATT_MTTKRP_U
+// lever set, streams that are not co-aligned, or the one instance that
+// would lose occupancy (below).
+// span is pick_span() rounded DOWN to a multiple of 32*R (R = 64/F groups
+// per wave: 256/128/64/32 at F = 8/16/32/64) so that every group's sub-span
+// is a whole number of 32-element windows. The 256 minimum and the 16384
+// clamp are multiples of all four, so both survive the rounding.
+template <typename V, typename S>
+bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
+                  int64_t goff, const int32_t * const idx[8],
+                  const S * const mats[8], const V * vals, int64_t nnz,
+                  V * out, int rank, int nother, hipStream_t st) {
+  if (!(rank == 8 || rank == 16 || rank == 32 || rank == 64)) return false;
+  if (nother < 2 || nother > 4 || pick_unroll() != 0) return false;
+  // the one instance whose 16-B staging costs occupancy: rank 8, 3 modes,
+  // f64 values and factors needs 102 (row pointers) / 106 (key) VGPRs
+  // against v2's 95, i.e. 4 waves/SIMD instead of 5, and forcing 5 spills
+  // to scratch. It stays on v2.
+  if (rank == 8 && nother == 2 && sizeof(V) == 8 && sizeof(S) == 8)
+    return false;
+  const int phase = stream_phase<V>(key, idx, nother, vals);
+  if (phase < 0) return false;
+  const int64_t quantum = 32 * (WAVE / rank);
+  const int64_t span = pick_span(nnz) / quantum * quantum;
+  const int64_t nwaves = (phase + nnz + span - 1) / span;
+  const int wpb = 4;
+  const int64_t nblocks = (nwaves + wpb - 1) / wpb;
+  dim3 grid((uint32_t)nblocks), block(wpb * WAVE);
+#define ARGS7 key, rowptr, nrows, goff, idx[0], idx[1], idx[2], idx[3], \
+              mats[0], mats[1], mats[2], mats[3], vals, nnz, span, phase, out
+#define L7(F_, N_) \
+  if (rowptr) \
+    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, true>), grid, block, \
+                       0, st, ARGS7); \
+  else \
+    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, false>), grid, \
+                       block, 0, st, ARGS7)
+#define L7F(N_) \
+  switch (rank) { case 8: L7(8, N_); break; case 16: L7(16, N_); break; \
+                  case 32: L7(32, N_); break; default: L7(64, N_); break; }
+  switch (nother) {
+    case 2: L7F(2); break;
+    case 3: L7F(3); break;
+    default: L7F(4); break;
+  }
+#undef L7F
+#undef L7
+#undef ARGS7
+  return true;
+}
+
+// storage-typed launcher (reduced-precision factor STORE for non-staged
+// HBM-bound dispatches): v7, else v2
 template <typename V, typename S>
 void launch_flat_store(const int32_t * key, const int32_t * const idx[8],
                        const S * const mats[8], const V * vals, int64_t nnz,
                        V * out, int rank, int nother, hipStream_t st) {
-  const int64_t span = pick_span_decl(nnz);
+  if (launch_flat7<V, S>(key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank,
+                         nother, st))
+    return;
+  const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
   const int wpb = 4;
   const int64_t nblocks = (nwaves + wpb - 1) / wpb;
@@ -489,32 +782,13 @@ mttkrp_flat_generic_kern(const int32_t * __restrict__ key,
   }
 }
 
-inline int64_t pick_span(int64_t nnz) {
-  const char * e = getenv("SPLATT_SPAN_WAVES");   // tuning knob
-  const int64_t target_waves = e ? atoll(e) : 65536;
-  int64_t span = nnz / target_waves;
-  if (span < 256) span = 256;
-  if (span > 16384) span = 16384;
-  return span;
-}
-
-inline int64_t pick_span_decl(int64_t nnz) { return pick_span(nnz); }
-
-inline bool spec_ok(int F) {
-  return F == 4 || F == 8 || F == 16 || F == 32 || F == 64;
-}
-
-inline int pick_unroll() {
-  // A/B lever: 0 (default) = staged v2 kernel; 4/8/16 = v1 at that unroll
-  const char * e = getenv("SPLATT_MTTKRP_U");
-  const int u = e ? atoi(e) : 0;
-  return (u == 2 || u == 3 || u == 4 || u == 5 || u == 8 || u == 16) ? u : 0;
-}
-
 template <typename V>
 void launch_flat(const int32_t * key, const int32_t * const idx[8],
                  const V * const mats[8], const V * vals, int64_t nnz,
                  V * out, int rank, int nother, hipStream_t st) {
+  if (launch_flat7<V, V>(key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank,
+                         nother, st))
+    return;
   const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
   const int wpb = 4;
@@ -591,7 +865,54 @@ extern "C" void splatt_hip_mttkrp_flat_f32(
                      (hipStream_t)stream);
 }
 
-// reduced-precision factor STORAGE (f64 accumulate) on the v2 path;
+// Row-pointer entry points (root output of a key-sorted stream): `rowptr`
+// (int64, nrows + 1 entries, GLOBAL stream positions) stands in for the key
+// stream; `p0` is the global stream position of the launch's first nonzero,
+// i.e. idx/vals point at element p0. Return 0 when launched, -1 when the
+// launch does not qualify for the v7 kernel (see launch_flat7) — the
+// caller then uses the key-stream entry points above.
+extern "C" int splatt_hip_mttkrp_flat_rp_f64(
+    const int64_t * rowptr, int64_t nrows, int64_t p0,
+    const int32_t * const * idx, const double * const * mats,
+    const double * vals, int64_t nnz, double * out, int rank, int nother,
+    void * stream) {
+  return launch_flat7<double, double>(nullptr, rowptr, nrows, p0, idx, mats,
+                                      vals, nnz, out, rank, nother,
+                                      (hipStream_t)stream) ? 0 : -1;
+}
+
+extern "C" int splatt_hip_mttkrp_flat_rp_f32(
+    const int64_t * rowptr, int64_t nrows, int64_t p0,
+    const int32_t * const * idx, const float * const * mats,
+    const float * vals, int64_t nnz, float * out, int rank, int nother,
+    void * stream) {
+  return launch_flat7<float, float>(nullptr, rowptr, nrows, p0, idx, mats,
+                                    vals, nnz, out, rank, nother,
+                                    (hipStream_t)stream) ? 0 : -1;
+}
+
+extern "C" int splatt_hip_mttkrp_flat_rp_f64f32(
+    const int64_t * rowptr, int64_t nrows, int64_t p0,
+    const int32_t * const * idx, const float * const * mats,
+    const double * vals, int64_t nnz, double * out, int rank, int nother,
+    void * stream) {
+  return launch_flat7<double, float>(nullptr, rowptr, nrows, p0, idx, mats,
+                                     vals, nnz, out, rank, nother,
+                                     (hipStream_t)stream) ? 0 : -1;
+}
+
+extern "C" int splatt_hip_mttkrp_flat_rp_f64bf16(
+    const int64_t * rowptr, int64_t nrows, int64_t p0,
+    const int32_t * const * idx, const uint16_t * const * mats,
+    const double * vals, int64_t nnz, double * out, int rank, int nother,
+    void * stream) {
+  return launch_flat7<double, bf16>(nullptr, rowptr, nrows, p0, idx,
+                                    (const bf16 * const *)mats, vals, nnz,
+                                    out, rank, nother,
+                                    (hipStream_t)stream) ? 0 : -1;
+}
+
+// reduced-precision factor STORAGE (f64 accumulate) on the v7/v2 path;
 // returns nonzero for unsupported (non-spec) ranks
 extern "C" int splatt_hip_mttkrp_flat_f64f32(
     const int32_t * key, const int32_t * const * idx,

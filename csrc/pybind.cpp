@@ -393,6 +393,19 @@ void splatt_hip_mttkrp_flat_f64(
 void splatt_hip_mttkrp_flat_f32(
     const int32_t*, const int32_t* const*, const float* const*,
     const float*, int64_t, float*, int, int, void*);
+// row-pointer variants (root output of a key-sorted stream); -1 = declined
+int splatt_hip_mttkrp_flat_rp_f64(
+    const int64_t*, int64_t, int64_t, const int32_t* const*,
+    const double* const*, const double*, int64_t, double*, int, int, void*);
+int splatt_hip_mttkrp_flat_rp_f32(
+    const int64_t*, int64_t, int64_t, const int32_t* const*,
+    const float* const*, const float*, int64_t, float*, int, int, void*);
+int splatt_hip_mttkrp_flat_rp_f64f32(
+    const int64_t*, int64_t, int64_t, const int32_t* const*,
+    const float* const*, const double*, int64_t, double*, int, int, void*);
+int splatt_hip_mttkrp_flat_rp_f64bf16(
+    const int64_t*, int64_t, int64_t, const int32_t* const*,
+    const uint16_t* const*, const double*, int64_t, double*, int, int, void*);
 // deterministic flat kernel, csrc/hip/mttkrp_det.hip
 int64_t splatt_hip_flat_det_ws(int64_t, int);
 int splatt_hip_mttkrp_flat_det_f64(
@@ -678,6 +691,56 @@ static void py_gpu_mttkrp_flat(Tensor key, std::vector<Tensor> idx,
   }
 }
 
+// Row-pointer form of the flat kernel: `rowptr` (int64, rows + 1 global
+// stream positions) replaces the key stream; idx/vals are the launch's
+// slices starting at global stream position p0. Returns false when the
+// launch does not qualify (the caller then takes gpu_mttkrp_flat).
+static bool py_gpu_mttkrp_flat_rp(Tensor rowptr, int64_t p0,
+                                  std::vector<Tensor> idx,
+                                  std::vector<Tensor> mats, Tensor vals,
+                                  Tensor out, int64_t stream) {
+  const int nother = (int)idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
+  TORCH_CHECK((int)mats.size() == nother);
+  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64 && rowptr.is_contiguous()
+              && rowptr.numel() >= 2 && rowptr.numel() <= out.size(0) + 1,
+              "rowptr must be contiguous int64 with at most rows + 1 entries");
+  const int rank = (int)mats[0].size(1);
+  const int64_t nnz = vals.numel();
+  const int64_t nrows = rowptr.numel() - 1;
+  const int64_t * rp = rowptr.data_ptr<int64_t>();
+  const int32_t * ip[8] = {};
+  for (int t = 0; t < nother; ++t) ip[t] = idx[t].data_ptr<int32_t>();
+  if (vals.scalar_type() == torch::kFloat64) {
+    if (mats[0].scalar_type() == torch::kFloat32) {
+      const float * mp[8] = {};
+      for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
+      return splatt_hip_mttkrp_flat_rp_f64f32(
+                 rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
+                 out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
+    }
+    if (mats[0].scalar_type() == torch::kBFloat16) {
+      const uint16_t * mp[8] = {};
+      for (int t = 0; t < nother; ++t)
+        mp[t] = reinterpret_cast<const uint16_t*>(
+            mats[t].data_ptr<at::BFloat16>());
+      return splatt_hip_mttkrp_flat_rp_f64bf16(
+                 rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
+                 out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
+    }
+    const double * mp[8] = {};
+    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
+    return splatt_hip_mttkrp_flat_rp_f64(
+               rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
+               out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
+  }
+  const float * mp[8] = {};
+  for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
+  return splatt_hip_mttkrp_flat_rp_f32(
+             rp, nrows, p0, ip, mp, vals.data_ptr<float>(), nnz,
+             out.data_ptr<float>(), rank, nother, (void*)stream) == 0;
+}
+
 // deterministic flat MTTKRP (csrc/hip/mttkrp_det.hip): plain stores for
 // walker-interior key runs + ordered fixup of boundary partials in `side`
 static void py_gpu_mttkrp_flat_det(Tensor key, std::vector<Tensor> idx,
@@ -907,6 +970,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_mttkrp3", &py_gpu_mttkrp3, "3-mode CSF MTTKRP HIP kernels");
   m.def("gpu_mttkrp_flat", &py_gpu_mttkrp_flat,
         "flat expanded-CSF MTTKRP HIP kernel (3..5 modes)");
+  m.def("gpu_mttkrp_flat_rp", &py_gpu_mttkrp_flat_rp,
+        "flat MTTKRP with row pointers in place of the key stream (root "
+        "output, key-sorted stream); false = declined, use gpu_mttkrp_flat");
   m.def("gpu_mttkrp_flat_det", &py_gpu_mttkrp_flat_det,
         "bitwise-deterministic flat MTTKRP (depth-0 streams, spec ranks)");
   m.def("flat_det_ws_elems", &splatt_hip_flat_det_ws,

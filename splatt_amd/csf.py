@@ -82,10 +82,17 @@ class Csf:
         stage = getattr(self, "_stage", None)
         if stage is not None:
             object.__setattr__(c, "_stage", dict(stage))
+        # root row pointers of the flat kernel (mttkrp.py _root_rowptr)
+        rowptr = getattr(self, "_rowptr", None)
+        if rowptr is not None:
+            object.__setattr__(c, "_rowptr", rowptr.to(device))
         return c
 
     def storage_bytes(self) -> int:
         b = self.vals.numel() * self.vals.element_size()
+        rowptr = getattr(self, "_rowptr", None)
+        if rowptr is not None:
+            b += rowptr.numel() * rowptr.element_size()
         pack = getattr(self, "_pack", None)
         if pack is not None:
             # expansions/leaf fids are strided views into the pack

@@ -143,6 +143,45 @@ def _key_bounds(c: Csf, depth: int, lo: int, hi: int) -> tuple:
     return cache[k]
 
 
+# Row-pointer gate: the root key stream is replaced by row pointers only
+# when runs are long, nnz >= _ROWPTR_MIN_RUN * dims[root] — the density
+# notion of the staging gate's min_run. Below it (a 17M-row Delicious mode
+# at 8 nnz/row) the 8-B boundary loads per run outweigh the 4 B/nnz of key
+# they replace, so those modes keep the key stream.
+_ROWPTR_MIN_RUN = 32
+
+
+def flat_rowptr_ok(c: Csf, depth: int, rank: int) -> bool:
+    """Does the unstaged flat dispatch of this mode read row pointers in
+    place of the key stream? Root output of a key-sorted stream, kernel
+    ranks 8/16/32/64, at most 5 modes, long runs; SPLATT_FLAT_ROWPTR=0
+    disables it. (The launcher may still decline — SPLATT_MTTKRP_U levers,
+    streams that are not co-aligned — and the dispatch then falls back to
+    the key stream.)"""
+    if os.environ.get("SPLATT_FLAT_ROWPTR") == "0":
+        return False
+    if depth != 0 or rank not in (8, 16, 32, 64) or c.nmodes > 5:
+        return False
+    if c.nnz < _ROWPTR_MIN_RUN * c.dims[c.dim_perm[0]]:
+        return False
+    return _key_sorted(c, depth)
+
+
+def _root_rowptr(c: Csf) -> torch.Tensor:
+    """int64 row pointers of the key-sorted root stream (dims[root] + 1
+    entries: rowptr[r] = first stream position with key >= r). Built once,
+    on first use, and kept on the Csf like the other per-stream caches."""
+    rp = getattr(c, "_rowptr", None)
+    if rp is None:
+        key = c.ancestor_expand(0).contiguous()
+        nrows = c.dims[c.dim_perm[0]]
+        rp = torch.searchsorted(
+            key, torch.arange(nrows + 1, dtype=key.dtype, device=key.device)
+        ).to(torch.int64).contiguous()
+        object.__setattr__(c, "_rowptr", rp)
+    return rp
+
+
 def _gpu_mttkrp_det(c: Csf, depth: int, mats: List[torch.Tensor],
                     out: torch.Tensor) -> None:
     """Bitwise-deterministic device MTTKRP (csrc/hip/mttkrp_det.hip):
@@ -296,6 +335,9 @@ def _gpu_mttkrp_flat(c: Csf, depth: int, mats: List[torch.Tensor],
             continue
         idx.append(c.ancestor_expand(l)[p0:p1].contiguous())
         ms.append(mats[c.dim_perm[l]].contiguous())
+    if flat_rowptr_ok(c, depth, rank) and native().gpu_mttkrp_flat_rp(
+            _root_rowptr(c), p0, idx, ms, c.vals[p0:p1], out, stream):
+        return
     native().gpu_mttkrp_flat(key[p0:p1].contiguous(), idx, ms,
                              c.vals[p0:p1], out, stream)
 
