@@ -267,34 +267,35 @@ template <typename V>
 __global__ void __launch_bounds__(256)
 gram_det_part_kern(const V * __restrict__ A, int64_t n, int F,
                    int64_t rows_per_blk, V * __restrict__ Gpart) {
-  const int e = threadIdx.x;
-  if (e >= F * F) return;
-  const int i = e / F, j = e % F;
   const int64_t r0 = (int64_t)blockIdx.x * rows_per_blk;
   const int64_t r1 = r0 + rows_per_blk < n ? r0 + rows_per_blk : n;
-  V acc = (V)0;
-  int64_t r = r0;
-  for (; r + 4 <= r1; r += 4) {
-    // four independent products -> the loads overlap the FMA chain
-    const V a0 = A[r * F + i] * A[r * F + j];
-    const V a1 = A[(r + 1) * F + i] * A[(r + 1) * F + j];
-    const V a2 = A[(r + 2) * F + i] * A[(r + 2) * F + j];
-    const V a3 = A[(r + 3) * F + i] * A[(r + 3) * F + j];
-    acc += (a0 + a1) + (a2 + a3);
+  // F*F can exceed the block (F > 16): each thread walks its elements
+  for (int e = threadIdx.x; e < F * F; e += blockDim.x) {
+    const int i = e / F, j = e % F;
+    V acc = (V)0;
+    int64_t r = r0;
+    for (; r + 4 <= r1; r += 4) {
+      // four independent products -> the loads overlap the FMA chain
+      const V a0 = A[r * F + i] * A[r * F + j];
+      const V a1 = A[(r + 1) * F + i] * A[(r + 1) * F + j];
+      const V a2 = A[(r + 2) * F + i] * A[(r + 2) * F + j];
+      const V a3 = A[(r + 3) * F + i] * A[(r + 3) * F + j];
+      acc += (a0 + a1) + (a2 + a3);
+    }
+    for (; r < r1; ++r) acc += A[r * F + i] * A[r * F + j];
+    Gpart[(int64_t)blockIdx.x * F * F + e] = acc;
   }
-  for (; r < r1; ++r) acc += A[r * F + i] * A[r * F + j];
-  Gpart[(int64_t)blockIdx.x * F * F + e] = acc;
 }
 
 template <typename V>
 __global__ void __launch_bounds__(256)
 gram_det_fold_kern(const V * __restrict__ Gpart, int64_t nparts, int F,
                    V * __restrict__ G) {
-  const int e = threadIdx.x;
-  if (e >= F * F) return;
-  V acc = (V)0;
-  for (int64_t b = 0; b < nparts; ++b) acc += Gpart[b * F * F + e];
-  G[e] = acc;
+  for (int e = threadIdx.x; e < F * F; e += blockDim.x) {
+    V acc = (V)0;
+    for (int64_t b = 0; b < nparts; ++b) acc += Gpart[b * F * F + e];
+    G[e] = acc;
+  }
 }
 
 template <typename V>

@@ -427,6 +427,10 @@ void splatt_hip_gram_f64(const double*, int64_t, int, double*, void*);
 void splatt_hip_gram_f32(const float*, int64_t, int, float*, void*);
 void splatt_hip_spd_inverse_f64(const double*, double*, int, void*);
 void splatt_hip_spd_inverse_f32(const float*, float*, int, void*);
+void splatt_hip_colacc_f64(const double*, int64_t, int, int, double*, void*);
+void splatt_hip_colscale_f64(double*, int64_t, int, const double*, void*);
+void splatt_hip_coldot_f64(const double*, const double*, int64_t, int,
+                           double*, void*);
 // LDS-staged flat kernel, csrc/hip/mttkrp_lds.hip
 void splatt_hip_mttkrp_flat5_f64(
     const int32_t*, const int32_t*, const int32_t*, const int32_t*,
@@ -978,6 +982,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flat_det_ws_elems", &splatt_hip_flat_det_ws,
         "workspace elements required by gpu_mttkrp_flat_det");
   m.def("gpu_gram", &py_gpu_gram, "G += A^T A (tall-skinny, F<=64)");
+  // column helpers of the C-API device driver (csrc/capi/capi_gpu.cpp)
+  m.def("gpu_colacc", [](Tensor A, int which, Tensor out, int64_t stream) {
+    check_dev(A, torch::kFloat64, "A");
+    check_dev(out, torch::kFloat64, "out");
+    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+                "A must be [n, F] with 1 <= F <= 64");
+    TORCH_CHECK(out.numel() == A.size(1), "out length != F");
+    TORCH_CHECK(which == 0 || which == 1,
+                "which: 0 = sum of squares, 1 = max |x|");
+    splatt_hip_colacc_f64(A.data_ptr<double>(), A.size(0), (int)A.size(1),
+                          which, out.data_ptr<double>(), (void*)stream);
+  }, "out[f] (pre-zeroed) += sum_i A[i,f]^2 (which=0), or "
+     "out[f] = max(out[f], max_i |A[i,f]|) (which=1)");
+  m.def("gpu_colscale", [](Tensor A, Tensor lam, int64_t stream) {
+    check_dev(A, torch::kFloat64, "A");
+    check_dev(lam, torch::kFloat64, "lam");
+    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+                "A must be [n, F] with 1 <= F <= 64");
+    TORCH_CHECK(lam.numel() == A.size(1), "lam length != F");
+    splatt_hip_colscale_f64(A.data_ptr<double>(), A.size(0), (int)A.size(1),
+                            lam.data_ptr<double>(), (void*)stream);
+  }, "A[i,f] /= lam[f] in place");
+  m.def("gpu_coldot", [](Tensor X, Tensor A, Tensor out, int64_t stream) {
+    check_dev(X, torch::kFloat64, "X");
+    check_dev(A, torch::kFloat64, "A");
+    check_dev(out, torch::kFloat64, "out");
+    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+                "A must be [n, F] with 1 <= F <= 64");
+    TORCH_CHECK(X.dim() == 2 && X.size(0) == A.size(0)
+                && X.size(1) == A.size(1), "X and A shapes differ");
+    TORCH_CHECK(out.numel() == A.size(1), "out length != F");
+    splatt_hip_coldot_f64(X.data_ptr<double>(), A.data_ptr<double>(),
+                          A.size(0), (int)A.size(1),
+                          out.data_ptr<double>(), (void*)stream);
+  }, "out[f] (pre-zeroed) += sum_i X[i,f] * A[i,f]");
   m.def("gpu_gram_det", [](Tensor A, Tensor Gpart, Tensor G,
                            int64_t stream) {
     const int64_t n = A.size(0);

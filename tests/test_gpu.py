@@ -438,6 +438,73 @@ def test_gpu_deterministic_graph_replay():
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize("rank", [16, 32, 64])
+def test_gpu_deterministic_cpd_matches_cpu(monkeypatch, rank):
+    """SPLATT_DETERMINISTIC=1 routes gram/solve through the atomic-free
+    dense kernels; the fit trace must still be the CPU's, at every spec
+    rank (F*F > 256 above rank 16)."""
+    t = sp.SpTensor.synthetic([60, 50, 70], 20_000, seed=53)
+    opts = sp.CpdOptions(max_iters=4, tolerance=0.0)
+    k_cpu = sp.cpd_als(t, rank, opts)
+    monkeypatch.setenv("SPLATT_DETERMINISTIC", "1")
+    k_gpu = sp.cpd_als(sp.csf_alloc(t.to("cuda"), "all"), rank, opts)
+    assert len(k_cpu.fit_trace) == len(k_gpu.fit_trace) == 4
+    for it, (a, b) in enumerate(zip(k_cpu.fit_trace, k_gpu.fit_trace)):
+        print(f"det cpd rank {rank} it {it}: cpu {a:.12f} gpu {b:.12f}")
+        assert abs(a - b) < 1e-6, (rank, it, a, b)
+
+
+def test_gpu_deterministic_graph_step_matches_eager(monkeypatch, t3):
+    """Deterministic twin of test_gpu_graph_step_matches_eager at rank 32:
+    the captured iteration keeps its Gram buffers across replays, so an
+    element gram_det does not rewrite stays at its iteration-0 value."""
+    from splatt_amd.parallel.dist_cpd import build_shard_csf
+    from splatt_amd.parallel.grid import GridDecomp, grid_cpd_init, grid_cpd_step
+    from splatt_amd.parallel.graph_exec import GraphStepRunner
+    monkeypatch.setenv("SPLATT_DETERMINISTIC", "1")
+    opts = sp.CpdOptions(max_iters=6, tolerance=0.0)
+    dec = GridDecomp.create(list(t3.dims))
+
+    cs = build_shard_csf(t3.to("cuda"), list(t3.dims), "all", flat_only=True,
+                         stage_rank=32)
+    st = grid_cpd_init(cs, dec, 32, opts)
+    grid_cpd_step(st, 0)
+    runner = GraphStepRunner(st)
+    assert runner.det
+    assert runner.capture(), runner.capture_error
+    for _ in range(3):
+        runner.replay()
+    fit_graph = runner.finalize(st.norm_x)
+    # the Gram buffers the replays kept must describe the final factors
+    # (dot-product forward bound, as in test_dense_gpu.py)
+    for m in range(3):
+        A = st.factors[m].cpu()
+        bound = 2 * A.shape[0] * 2.0 ** -53 * (A.abs().T @ A.abs())
+        err = (st.grams[m].cpu() - A.T @ A).abs()
+        assert bool((err <= bound).all()), (m, float((err / bound).max()))
+
+    st2 = grid_cpd_init(cs, dec, 32, opts)
+    for it in range(6):  # 1 eager + 2 warmup-in-capture + 3 replays
+        fit_eager = grid_cpd_step(st2, it)
+    assert abs(fit_graph - fit_eager) < 1e-6, (fit_graph, fit_eager)
+
+
+@pytest.mark.parametrize("rank", [4, 8, 64])
+def test_gpu_deterministic_matches_oracle_other_ranks(rank):
+    """Ranks 4 and 64 have 16 and 1 sub-spans per wave."""
+    t = sp.SpTensor.synthetic([40, 30, 50], 6_000, seed=31)
+    mats_c = make_mats(t.dims, rank)
+    mats_g = [m.cuda() for m in mats_c]
+    cs = sp.csf_alloc(t.to("cuda"), "all")
+    for mode in range(3):
+        out = sp.mttkrp(cs, mats_g, mode, deterministic=True)
+        ref = sp.mttkrp_stream(t, mats_c, mode)
+        err = (out.cpu() - ref).abs().max().item()
+        assert err < 1e-8, (rank, mode, err)
+        again = sp.mttkrp(cs, mats_g, mode, deterministic=True)
+        assert torch.equal(out, again), (rank, mode)
+
+
 def test_gpu_cpd_regularize():
     t = sp.SpTensor.synthetic([100, 80, 120], 30_000, seed=19)
     o0 = sp.CpdOptions(max_iters=5, tolerance=0.0, seed=3)
