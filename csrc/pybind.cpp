@@ -954,7 +954,56 @@ static void py_gpu_kruskal_predict(Tensor inds, std::vector<Tensor> mats,
               splatt_hip_complete_errstr(rc));
 }
 
+// ------------------------------------- constrained CPD / AO-ADMM (f64 only)
+extern "C" {
+// csrc/hip/admm.hip; nonzero return = hipError_t of the launch
+int splatt_hip_admm_update_f64(
+    const double*, const double*, const double*, double*, double*, int32_t*,
+    int64_t, int, int, double, double, double, double, int, int, void*);
+}
+
+// The fused block-ADMM update of one factor: H and U are updated in place,
+// iters receives one inner-iteration count per block of 64 rows.
+static void py_gpu_admm_update(Tensor K, Tensor Ginv, Tensor rho, Tensor H,
+                               Tensor U, Tensor iters, int64_t kind, double w,
+                               double lo, double hi, double inner_tol,
+                               int64_t max_inner, int64_t variant,
+                               int64_t stream) {
+  check_dev(K, torch::kFloat64, "K");
+  check_dev(Ginv, torch::kFloat64, "Ginv");
+  check_dev(rho, torch::kFloat64, "rho");
+  check_dev(H, torch::kFloat64, "H");
+  check_dev(U, torch::kFloat64, "U");
+  check_dev(iters, torch::kInt32, "iters");
+  TORCH_CHECK(H.dim() == 2, "H must be [rows, rank]");
+  const int64_t n = H.size(0);
+  const int F = (int)H.size(1);
+  TORCH_CHECK(F >= 1 && F <= 64, "admm_update supports rank 1..64, got ", F);
+  TORCH_CHECK(K.sizes() == H.sizes() && U.sizes() == H.sizes(),
+              "K, H and U must have the same shape");
+  TORCH_CHECK(Ginv.dim() == 2 && Ginv.size(0) == F && Ginv.size(1) == F,
+              "Ginv must be [rank, rank]");
+  TORCH_CHECK(rho.numel() == 1, "rho must have one element");
+  TORCH_CHECK(iters.numel() == (n + 63) / 64,
+              "iters must have one entry per block of 64 rows");
+  TORCH_CHECK(kind >= 0 && kind <= 3, "unknown constraint kind ", kind);
+  TORCH_CHECK(max_inner >= 0 && max_inner <= 0x7FFFFFFF,
+              "max_inner out of range");
+  TORCH_CHECK(variant == 0 || variant == 1
+              || (variant == 2 && (F == 16 || F == 32 || F == 64)),
+              "the MFMA variant exists for ranks 16, 32 and 64 only");
+  const int rc = splatt_hip_admm_update_f64(
+      K.data_ptr<double>(), Ginv.data_ptr<double>(), rho.data_ptr<double>(),
+      H.data_ptr<double>(), U.data_ptr<double>(), iters.data_ptr<int32_t>(),
+      n, F, (int)kind, w, lo, hi, inner_tol, (int)max_inner, (int)variant,
+      (void*)stream);
+  TORCH_CHECK(rc == 0, "admm_update kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gpu_admm_update", &py_gpu_admm_update,
+        "fused block-ADMM factor update (in place on H, U)");
   m.def("gpu_complete_update", &py_gpu_complete_update,
         "row-wise completion update: one batch of segments + row solves");
   m.def("complete_slot_elems", &splatt_hip_complete_slot_elems,

@@ -18,6 +18,9 @@ from splatt_amd.kruskal import (kruskal_fit, kruskal_innerprod, kruskal_norm,
                                 kruskal_to_dense)
 from splatt_amd.completion import (CompleteOptions, Completion, complete_als,
                                    complete_update, kruskal_predict, rmse)
+from splatt_amd.admm import (AoAdmmOptions, Constraint, ConstrainedKruskal,
+                             admm_solve, admm_update, box, cpd_aoadmm, l1,
+                             nonneg, nonneg_l1)
 
 load = SpTensor.load
 
@@ -28,4 +31,6 @@ __all__ = [
     "kruskal_fit", "kruskal_innerprod", "kruskal_norm", "kruskal_to_dense",
     "CompleteOptions", "Completion", "complete_als", "complete_update",
     "kruskal_predict", "rmse",
+    "AoAdmmOptions", "Constraint", "ConstrainedKruskal", "admm_solve",
+    "admm_update", "cpd_aoadmm", "nonneg", "l1", "nonneg_l1", "box",
 ]

@@ -79,8 +79,68 @@ def cmd_complete(args) -> int:
     return 0
 
 
+def parse_constraints(specs, nmodes: int):
+    """`--con` specs -> per-mode list of Constraint / None.
+
+    SPEC = KIND[:ARG[:ARG]][@MODES]; MODES is a comma list of 1-based modes
+    (the numbering of the modeN.mat files), default every mode."""
+    from splatt_amd.admm import KINDS, Constraint
+    nargs = {"nonneg": 0, "l1": 1, "nonneg_l1": 1, "box": 2}
+    out = [None] * nmodes
+    for spec in specs:
+        body, at, modes_s = spec.partition("@")
+        parts = body.split(":")
+        kind = parts[0]
+        if kind not in KINDS:
+            raise ValueError(f"--con {spec!r}: unknown kind {kind!r} "
+                             f"({', '.join(KINDS)})")
+        if len(parts) - 1 != nargs[kind]:
+            raise ValueError(f"--con {spec!r}: {kind} takes {nargs[kind]} "
+                             f"argument(s), got {len(parts) - 1}")
+        try:
+            vals = [float(x) for x in parts[1:]]
+        except ValueError:
+            raise ValueError(f"--con {spec!r}: arguments must be numbers")
+        try:
+            if kind == "box":
+                con = Constraint(kind, lo=vals[0], hi=vals[1])
+            elif vals:
+                con = Constraint(kind, weight=vals[0])
+            else:
+                con = Constraint(kind)
+        except ValueError as e:
+            raise ValueError(f"--con {spec!r}: {e}")
+        if at:
+            try:
+                modes = [int(x) for x in modes_s.split(",")]
+            except ValueError:
+                raise ValueError(f"--con {spec!r}: modes must be a comma "
+                                 "list of integers")
+        else:
+            modes = list(range(1, nmodes + 1))
+        for m in modes:
+            if not 1 <= m <= nmodes:
+                raise ValueError(f"--con {spec!r}: mode {m} out of range "
+                                 f"1..{nmodes}")
+            if out[m - 1] is not None:
+                raise ValueError(f"--con {spec!r}: mode {m} is constrained "
+                                 "twice")
+            out[m - 1] = con
+    return out
+
+
 def cmd_cpd(args) -> int:
     import os
+    con_specs = getattr(args, "con", None) or []
+    if con_specs:
+        if args.native:
+            raise ValueError("--con cannot be combined with --native")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError("--con is not supported by the distributed "
+                             "driver (WORLD_SIZE > 1)")
+        if args.dtype != "f64":
+            raise ValueError("--con supports float64 tensors only "
+                             "(--dtype f64)")
     if getattr(args, "csf", None) is None:
         use_cuda = (args.device in ("auto", "cuda")
                     and torch.cuda.is_available())
@@ -101,6 +161,18 @@ def cmd_cpd(args) -> int:
                          seed=args.seed, csf_alloc=args.csf,
                          nthreads=args.nthreads, verbose=args.verbose > 0,
                          regularize=args.reg)
+    cons = parse_constraints(con_specs, t.nmodes) if con_specs else None
+
+    def run(cs):
+        if cons is None:
+            return sp.cpd_als(cs, args.rank, opts)
+        aopts = sp.AoAdmmOptions(
+            tolerance=args.tol, max_iters=args.its, seed=args.seed,
+            csf_alloc=args.csf, nthreads=args.nthreads,
+            verbose=args.verbose > 0, regularize=args.reg,
+            inner_tol=args.inner_tol, max_inner=args.inner_its)
+        return sp.cpd_aoadmm(cs, args.rank, cons, aopts)
+
     dev = args.device
     if dev == "auto":
         dev = "cuda" if torch.cuda.is_available() else "cpu"
@@ -116,13 +188,17 @@ def cmd_cpd(args) -> int:
                                  flat_only=True, stage_rank=stage)
             print(stats_csf(cs))
             print(cpd_stats(cs, args.rank, opts))
-            k = sp.cpd_als(cs, args.rank, opts)
+            k = run(cs)
         else:
             cs = sp.csf_alloc(t.to(dev), args.csf)
             print(stats_csf(cs))
             print(cpd_stats(cs, args.rank, opts))
-            k = sp.cpd_als(cs, args.rank, opts)
-    print(f"Final fit: {k.fit:.5f}  (iterations: {k.niters})")
+            k = run(cs)
+    if cons is not None:
+        print(f"Final fit: {k.fit:.5f}  (iterations: {k.niters}; inner "
+              f"iterations: {sum(sum(r) for r in k.inner_iters)})")
+    else:
+        print(f"Final fit: {k.fit:.5f}  (iterations: {k.niters})")
     if not args.nowrite:
         for m, f in enumerate(k.factors):
             _write_matrix(f"mode{m + 1}.mat", f)
@@ -300,6 +376,16 @@ def main(argv=None) -> int:
     p.add_argument("--deterministic", action="store_true",
                    help="bitwise-reproducible device CPD (atomic-free "
                         "kernels, >=80%% throughput; implies --csf all)")
+    p.add_argument("--con", action="append", default=[], metavar="SPEC",
+                   help="constrained CPD (AO-ADMM); repeatable. SPEC = "
+                        "KIND[:ARG[:ARG]][@MODES] with KIND nonneg, l1:W, "
+                        "nonneg_l1:W or box:LO:HI and MODES a comma list of "
+                        "1-based modes (default: every mode), e.g. "
+                        "--con nonneg, --con l1:0.1@1,3, --con box:0:1@2")
+    p.add_argument("--inner-its", type=int, default=50,
+                   help="ADMM inner iteration bound per block (--con)")
+    p.add_argument("--inner-tol", type=float, default=1e-2,
+                   help="ADMM inner stopping tolerance (--con)")
     p.add_argument("-v", "--verbose", action="count", default=0)
     p.set_defaults(fn=cmd_cpd)
 
