@@ -954,6 +954,89 @@ static void py_gpu_kruskal_predict(Tensor inds, std::vector<Tensor> mats,
               splatt_hip_complete_errstr(rc));
 }
 
+// ------------------------------------------------ Tucker / TTMc (f64 only)
+extern "C" {
+// csrc/hip/ttmc.hip; nonzero return = hipError_t of the launch
+int splatt_hip_ttmc_max_cols();
+int splatt_hip_ttmc_segments_f64(
+    const int32_t* const*, const double* const*, const int*, int,
+    const double*, const int64_t*, const int32_t*, const int32_t*,
+    const int32_t*, int64_t, int64_t, int64_t, double*, double*, void*);
+int splatt_hip_ttmc_reduce_f64(
+    const double*, const int32_t*, const int64_t*, int64_t, int64_t, int64_t,
+    int, double*, void*);
+}
+
+// One batch of the TTMc of a root-sorted stream: segments [seg0, seg0+nseg)
+// accumulate (single-segment rows go straight to `out`), then multi-segment
+// rows [m0, m0+nm) are folded from `ws`. idx/mats are the non-root levels
+// in level order; `out` is [rows, prod of their ranks] in that order. Slots
+// slot0..slot0+nslots-1 (one output row each) live in `ws` during the batch.
+static void py_gpu_ttmc(
+    std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
+    Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
+    int64_t seg0, int64_t nseg, Tensor mrow, Tensor mslot, int64_t m0,
+    int64_t nm, int64_t slot0, int64_t nslots, Tensor ws, Tensor out,
+    int64_t stream) {
+  const int nother = (int)idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "ttmc supports 3..8 modes");
+  TORCH_CHECK((int)mats.size() == nother);
+  check_dev(vals, torch::kFloat64, "vals");
+  check_dev(out, torch::kFloat64, "out");
+  check_dev(ws, torch::kFloat64, "ws");
+  check_dev(seg_start, torch::kInt64, "seg_start");
+  check_dev(seg_len, torch::kInt32, "seg_len");
+  check_dev(seg_row, torch::kInt32, "seg_row");
+  check_dev(seg_slot, torch::kInt32, "seg_slot");
+  check_dev(mrow, torch::kInt32, "mrow");
+  check_dev(mslot, torch::kInt64, "mslot");
+  TORCH_CHECK(out.dim() == 2, "out must be [rows, columns]");
+  const int64_t nnz = vals.numel();
+  const int32_t * ip[8] = {};
+  const double * mp[8] = {};
+  int ranks[8] = {};
+  int64_t P = 1;
+  for (int t = 0; t < nother; ++t) {
+    check_dev(idx[t], torch::kInt32, "idx");
+    check_dev(mats[t], torch::kFloat64, "factor");
+    TORCH_CHECK(idx[t].numel() == nnz, "index stream length != nnz");
+    TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) >= 1
+                && mats[t].size(1) <= 32,
+                "ttmc supports rank 1..32 per mode, got ", mats[t].size(1));
+    ip[t] = idx[t].data_ptr<int32_t>();
+    mp[t] = mats[t].data_ptr<double>();
+    ranks[t] = (int)mats[t].size(1);
+    P *= ranks[t];
+  }
+  TORCH_CHECK(P <= splatt_hip_ttmc_max_cols(), "ttmc kernel supports at most ",
+              splatt_hip_ttmc_max_cols(), " output columns, got ", P);
+  TORCH_CHECK(out.size(1) == P, "out has ", out.size(1), " columns, expected ",
+              P);
+  TORCH_CHECK(seg_len.numel() == seg_start.numel()
+              && seg_row.numel() == seg_start.numel()
+              && seg_slot.numel() == seg_start.numel());
+  TORCH_CHECK(seg0 >= 0 && nseg >= 0 && seg0 + nseg <= seg_start.numel(),
+              "segment range out of bounds");
+  TORCH_CHECK(m0 >= 0 && nm >= 0 && m0 + nm <= mrow.numel()
+              && mslot.numel() == mrow.numel() + 1,
+              "multi-segment row range out of bounds");
+  TORCH_CHECK(nslots >= 0 && slot0 >= 0 && ws.numel() >= nslots * P,
+              "ttmc workspace too small");
+  int rc = splatt_hip_ttmc_segments_f64(
+      ip, mp, ranks, nother, vals.data_ptr<double>(),
+      seg_start.data_ptr<int64_t>(), seg_len.data_ptr<int32_t>(),
+      seg_row.data_ptr<int32_t>(), seg_slot.data_ptr<int32_t>(), seg0, nseg,
+      slot0, ws.data_ptr<double>(), out.data_ptr<double>(), (void*)stream);
+  TORCH_CHECK(rc == 0, "ttmc segment kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+  rc = splatt_hip_ttmc_reduce_f64(
+      ws.data_ptr<double>(), mrow.data_ptr<int32_t>(),
+      mslot.data_ptr<int64_t>(), m0, nm, slot0, (int)P,
+      out.data_ptr<double>(), (void*)stream);
+  TORCH_CHECK(rc == 0, "ttmc reduce kernel launch failed: ",
+              splatt_hip_complete_errstr(rc));
+}
+
 // ------------------------------------- constrained CPD / AO-ADMM (f64 only)
 extern "C" {
 // csrc/hip/admm.hip; nonzero return = hipError_t of the launch
@@ -1004,6 +1087,10 @@ static void py_gpu_admm_update(Tensor K, Tensor Ginv, Tensor rho, Tensor H,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_admm_update", &py_gpu_admm_update,
         "fused block-ADMM factor update (in place on H, U)");
+  m.def("gpu_ttmc", &py_gpu_ttmc,
+        "TTMc of a root-sorted stream: one batch of segments + row folds");
+  m.def("ttmc_max_cols", &splatt_hip_ttmc_max_cols,
+        "widest TTMc output row the HIP kernel supports");
   m.def("gpu_complete_update", &py_gpu_complete_update,
         "row-wise completion update: one batch of segments + row solves");
   m.def("complete_slot_elems", &splatt_hip_complete_slot_elems,

@@ -21,6 +21,7 @@ from splatt_amd.completion import (CompleteOptions, Completion, complete_als,
 from splatt_amd.admm import (AoAdmmOptions, Constraint, ConstrainedKruskal,
                              admm_solve, admm_update, box, cpd_aoadmm, l1,
                              nonneg, nonneg_l1)
+from splatt_amd.tucker import Tucker, TuckerOptions, ttmc, tucker_hooi
 
 load = SpTensor.load
 
@@ -33,4 +34,5 @@ __all__ = [
     "kruskal_predict", "rmse",
     "AoAdmmOptions", "Constraint", "ConstrainedKruskal", "admm_solve",
     "admm_update", "cpd_aoadmm", "nonneg", "l1", "nonneg_l1", "box",
+    "Tucker", "TuckerOptions", "ttmc", "tucker_hooi",
 ]

@@ -79,6 +79,50 @@ def cmd_complete(args) -> int:
     return 0
 
 
+def cmd_tucker(args) -> int:
+    """`splatt tucker`: sparse Tucker decomposition by HOOI. Writes
+    <stem>modeN.mat per mode and the core as <stem>core.tns (every entry,
+    1-based coordinates)."""
+    import os
+    if args.dtype != "f64":
+        raise ValueError("tucker supports float64 tensors only "
+                         "(--dtype f64)")
+    try:
+        ranks = [int(x) for x in args.rank.split(",")]
+    except ValueError:
+        raise ValueError(f"-r {args.rank!r}: ranks must be a comma list of "
+                         "integers, one per mode")
+    t = _load(args)
+    print(stats_tt(t, args.tensor))
+    dev = args.device
+    if dev == "auto":
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+    opts = sp.TuckerOptions(max_iters=args.its, tol=args.tol, seed=args.seed,
+                            verbosity=1)
+    with TIMERS.time("TUCKER"):
+        cs = sp.csf_alloc(t.to(dev), "all")
+        print(stats_csf(cs))
+        r = sp.tucker_hooi(cs, ranks, opts)
+    print(f"Final fit: {r.fit:.6f}  (iterations: {r.iters})")
+    if not args.nowrite:
+        parent = os.path.dirname(args.stem)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        for m, f in enumerate(r.factors):
+            _write_matrix(f"{args.stem}mode{m + 1}.mat", f)
+        core = r.core.cpu()
+        coords = torch.cartesian_prod(
+            *[torch.arange(n) for n in core.shape]).reshape(-1, core.dim())
+        with open(f"{args.stem}core.tns", "w") as fh:
+            for idx, x in zip(coords.tolist(), core.reshape(-1).tolist()):
+                fh.write(" ".join(str(i + 1) for i in idx) + f" {x:.17g}\n")
+        print(f"wrote {len(r.factors)} factor matrices and core.tns "
+              f"({'x'.join(str(n) for n in core.shape)}) with stem "
+              f"{args.stem!r}")
+    print(TIMERS.report())
+    return 0
+
+
 def parse_constraints(specs, nmodes: int):
     """`--con` specs -> per-mode list of Constraint / None.
 
@@ -409,6 +453,23 @@ def main(argv=None) -> int:
                    metavar="DIR",
                    help="write modeN.mat factor files (into DIR, default .)")
     p.set_defaults(fn=cmd_complete)
+
+    p = sub.add_parser("tucker",
+                       help="sparse Tucker decomposition (HOOI)")
+    _add_common(p)
+    p.add_argument("-r", "--rank", default="8,8,8", metavar="R1,R2,..",
+                   help="comma list of ranks, one per mode (each 1..32)")
+    p.add_argument("-i", "--iters", "--its", dest="its", type=int,
+                   default=50)
+    p.add_argument("-t", "--tol", type=float, default=1e-5,
+                   help="stop when the fit changes by less than this")
+    p.add_argument("--seed", type=int, default=0x5EED5EED)
+    p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    p.add_argument("--stem", default="", metavar="PATH",
+                   help="prefix of the output files PATHmodeN.mat and "
+                        "PATHcore.tns (end it with / for a directory)")
+    p.add_argument("--nowrite", action="store_true")
+    p.set_defaults(fn=cmd_tucker)
 
     p = sub.add_parser("check", help="find/repair duplicates + empty slices")
     _add_common(p)
