@@ -153,20 +153,51 @@ void launch_gram(const V * A, int64_t n, int F, V * G, hipStream_t st) {
 // info sync that breaks hipGraph capture) for the ALS normal equations.
 // On breakdown (non-positive pivot) retries with escalating Tikhonov
 // jitter, like the host solver (csrc/core/matrix.cpp solve_normals).
+//
+// The input is the Hadamard product of up to 8 F x F matrices (the other
+// modes' Grams of an ALS update, multiplied left to right) plus `reg` on
+// the diagonal, formed while it is loaded: no G.copy_/G.mul_ chain in
+// front. The same launch also resets the accumulators of the fused ALS
+// tail (als_tail.hip) when asked: zero_gram (F x F) and zero_inner (F) to
+// 0, lam_init (F) to 1. An empty table does only that.
+template <typename V>
+struct HadTab {
+  const V * g[8];
+  int n;
+};
+
+template <typename V>
+__device__ __forceinline__ V had_at(const HadTab<V> & t, int e, int F, V reg) {
+  V x = t.g[0][e];
+  #pragma unroll
+  for (int o = 1; o < 8; ++o)     // constant indices: the table stays in
+    if (o < t.n) x *= t.g[o][e];  // the kernel-argument segment
+  if (reg != (V)0 && e / F == e % F) x += reg;
+  return x;
+}
+
 template <typename V>
 __global__ void __launch_bounds__(64)
-spd_inverse_kern(const V * __restrict__ G, V * __restrict__ Ginv, int F) {
+spd_inverse_kern(const HadTab<V> tab, V reg, V * __restrict__ Ginv, int F,
+                 V * __restrict__ zero_gram, V * __restrict__ lam_init,
+                 V * __restrict__ zero_inner) {
   // one 32KB LDS array; Ginv doubles as scratch for X = L^-1
   __shared__ V Lm[64 * 64];
   __shared__ V diagmax_sh;
   __shared__ int fail_sh;
   const int tid = threadIdx.x;
 
+  if (zero_gram)
+    for (int e = tid; e < F * F; e += 64) zero_gram[e] = (V)0;
+  if (lam_init && tid < F) lam_init[tid] = (V)1;
+  if (zero_inner && tid < F) zero_inner[tid] = (V)0;
+  if (tab.n == 0) return;
+
   V jitter = (V)0;
   if (tid == 0) {
     V mx = (V)0;
     for (int j = 0; j < F; ++j) {
-      const V d = G[j * F + j];
+      const V d = had_at(tab, j * F + j, F, reg);
       mx = mx > d ? mx : d;
     }
     diagmax_sh = mx;
@@ -175,7 +206,7 @@ spd_inverse_kern(const V * __restrict__ G, V * __restrict__ Ginv, int F) {
   const V diagmax = diagmax_sh;
 
   for (int attempt = 0; attempt < 24; ++attempt) {
-    for (int e = tid; e < F * F; e += 64) Lm[e] = G[e];
+    for (int e = tid; e < F * F; e += 64) Lm[e] = had_at(tab, e, F, reg);
     if (tid == 0) fail_sh = 0;
     __syncthreads();
     if (jitter > (V)0 && tid < F) Lm[tid * F + tid] += jitter;
@@ -438,11 +469,38 @@ extern "C" void splatt_hip_gram_f32(const float * A, int64_t n, int F,
 }
 extern "C" void splatt_hip_spd_inverse_f64(const double * G, double * Ginv,
                                            int F, void * stream) {
+  HadTab<double> tab{};
+  tab.g[0] = G;
+  tab.n = 1;
   hipLaunchKernelGGL((spd_inverse_kern<double>), dim3(1), dim3(64), 0,
-                     (hipStream_t)stream, G, Ginv, F);
+                     (hipStream_t)stream, tab, 0.0, Ginv, F,
+                     (double *)nullptr, (double *)nullptr, (double *)nullptr);
 }
 extern "C" void splatt_hip_spd_inverse_f32(const float * G, float * Ginv,
                                            int F, void * stream) {
+  HadTab<float> tab{};
+  tab.g[0] = G;
+  tab.n = 1;
   hipLaunchKernelGGL((spd_inverse_kern<float>), dim3(1), dim3(64), 0,
-                     (hipStream_t)stream, G, Ginv, F);
+                     (hipStream_t)stream, tab, 0.0f, Ginv, F,
+                     (float *)nullptr, (float *)nullptr, (float *)nullptr);
+}
+
+// Front of the fused ALS tail (als_tail.hip), one launch: Ginv = inverse of
+// (grams[0] .* ... .* grams[ngrams-1] + reg*I), and the tail's accumulators
+// reset (any of the three may be null). ngrams == 0 only resets. Returns
+// the launch status (0 = ok), -1 for F > 64 or more than 8 matrices.
+extern "C" int splatt_hip_als_prep_f64(const double * const * grams,
+                                       int ngrams, double reg, double * Ginv,
+                                       int F, double * zero_gram,
+                                       double * lam_init, double * zero_inner,
+                                       void * stream) {
+  if (F < 1 || F > 64 || ngrams < 0 || ngrams > 8) return -1;
+  HadTab<double> tab{};
+  for (int o = 0; o < ngrams; ++o) tab.g[o] = grams[o];
+  tab.n = ngrams;
+  hipLaunchKernelGGL((spd_inverse_kern<double>), dim3(1), dim3(64), 0,
+                     (hipStream_t)stream, tab, reg, Ginv, F, zero_gram,
+                     lam_init, zero_inner);
+  return (int)hipGetLastError();
 }

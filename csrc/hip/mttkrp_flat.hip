@@ -224,6 +224,10 @@ mttkrp_flat2_kern(const int32_t * __restrict__ key,
 //   vals (f64)     NVL = 2 loads of 128 B each for F <= 16 (element e:
 //                  load e/CH, lane gbase + (e%CH)/VPL, component e%VPL);
 //                  f32 vals follow the int32 layout
+// The value STREAM type VS is separate from the compute type V: VS = float
+// with V = double reads a 4-byte copy of values that are all f32-exact
+// (splatt_amd/mttkrp.py narrows once per CSF) with the int32 layout, one
+// load per window, and widens each value once after the shuffle.
 // Windows are aligned to 32 elements of the underlying allocation: the
 // launcher passes `phase` (elements from the preceding 128-B boundary to
 // the first element) and rounds span so sub-spans start on window
@@ -249,7 +253,7 @@ __device__ __forceinline__ void ldnt_vec(const T * p, T (&r)[N]) {
   }
 }
 
-template <typename V, int F, int NOTHER, typename S, bool RP>
+template <typename V, int F, int NOTHER, typename S, bool RP, typename VS = V>
 __global__ void __launch_bounds__(256)
 mttkrp_flat7_kern(const int32_t * __restrict__ key,
                   const int64_t * __restrict__ rowptr, int64_t nrows,
@@ -260,12 +264,12 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
                   const int32_t * __restrict__ i3,
                   const S * __restrict__ m0, const S * __restrict__ m1,
                   const S * __restrict__ m2, const S * __restrict__ m3,
-                  const V * __restrict__ vals, int64_t nnz, int64_t span,
+                  const VS * __restrict__ vals, int64_t nnz, int64_t span,
                   int phase, V * __restrict__ out) {
   constexpr int R = WAVE / F;
   constexpr int W = 32;                          // stream window (nnz)
   constexpr int EPL = (F >= W) ? 1 : W / F;      // int32 elements per lane
-  constexpr int VPL = (sizeof(V) == 8 && EPL > 1) ? EPL / 2 : EPL;
+  constexpr int VPL = (sizeof(VS) == 8 && EPL > 1) ? EPL / 2 : EPL;
   constexpr int NVL = EPL / VPL;                 // vals loads per window
   constexpr int CH = W / NVL;                    // elements per vals load
   constexpr int GB = 8;                          // gather sub-batch
@@ -335,7 +339,7 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
     if (qb >= a && qb + W <= b) {
       const int64_t ps = pw + slot * EPL;
       int32_t kreg[EPL], i0reg[EPL], i1reg[EPL], i2reg[EPL], i3reg[EPL];
-      V vreg[NVL][VPL];
+      VS vreg[NVL][VPL];
       if constexpr (!RP) ldnt_vec(key + ps, kreg);
       ldnt_vec(i0 + ps, i0reg);
       ldnt_vec(i1 + ps, i1reg);
@@ -358,7 +362,8 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
           #pragma unroll
           for (int u = 0; u < GB; ++u) {
             const int src = gbase + ub / EPL + u / EPL;
-            vv[u] = __shfl(vreg[k][u % VPL], gbase + h / VPL + u / VPL, WAVE);
+            vv[u] = (V)__shfl(vreg[k][u % VPL], gbase + h / VPL + u / VPL,
+                              WAVE);
             const int32_t j0 = __shfl(i0reg[u % EPL], src, WAVE);
             const int32_t j1 = __shfl(i1reg[u % EPL], src, WAVE);
             a0[u] = m0[(int64_t)j0 * F + c];
@@ -393,7 +398,7 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
       const int e1 = (int)(min64(b, qb + W) - qb);
       for (int e = e0; e < e1; ++e) {
         const int64_t p = pw + e;
-        V x = ldnt(&vals[p])
+        V x = (V)ldnt(&vals[p])
               * to_compute(m0[(int64_t)ldnt(&i0[p]) * F + c], (V)0)
               * to_compute(m1[(int64_t)ldnt(&i1[p]) * F + c], (V)0);
         if constexpr (NOTHER > 2)
@@ -435,15 +440,15 @@ inline int pick_unroll() {
 // Elements between the preceding 128-B line boundary of the int32 streams
 // and their first element, or -1 when the streams of this launch are not
 // co-aligned (some stream's line boundaries fall on other elements).
-template <typename V>
+template <typename VS>
 inline int stream_phase(const int32_t * key, const int32_t * const idx[8],
-                        int nother, const V * vals) {
+                        int nother, const VS * vals) {
   const int phase = (int)(((uintptr_t)idx[0] >> 2) & 31);
   if (key && (int)(((uintptr_t)key >> 2) & 31) != phase) return -1;
   for (int t = 1; t < nother; ++t)
     if ((int)(((uintptr_t)idx[t] >> 2) & 31) != phase) return -1;
-  if ((uintptr_t)vals % sizeof(V)) return -1;
-  if ((int)(((uintptr_t)vals / sizeof(V)) & 31) != phase) return -1;
+  if ((uintptr_t)vals % sizeof(VS)) return -1;
+  if ((int)(((uintptr_t)vals / sizeof(VS)) & 31) != phase) return -1;
   return phase;
 }
 
@@ -456,20 +461,21 @@ inline int stream_phase(const int32_t * key, const int32_t * const idx[8],
 // per wave: 256/128/64/32 at F = 8/16/32/64) so that every group's sub-span
 // is a whole number of 32-element windows. The 256 minimum and the 16384
 // clamp are multiples of all four, so both survive the rounding.
-template <typename V, typename S>
+template <typename V, typename S, typename VS = V>
 bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
                   int64_t goff, const int32_t * const idx[8],
-                  const S * const mats[8], const V * vals, int64_t nnz,
+                  const S * const mats[8], const VS * vals, int64_t nnz,
                   V * out, int rank, int nother, hipStream_t st) {
   if (!(rank == 8 || rank == 16 || rank == 32 || rank == 64)) return false;
   if (nother < 2 || nother > 4 || pick_unroll() != 0) return false;
   // the one instance whose 16-B staging costs occupancy: rank 8, 3 modes,
   // f64 values and factors needs 102 (row pointers) / 106 (key) VGPRs
   // against v2's 95, i.e. 4 waves/SIMD instead of 5, and forcing 5 spills
-  // to scratch. It stays on v2.
-  if (rank == 8 && nother == 2 && sizeof(V) == 8 && sizeof(S) == 8)
+  // to scratch. It stays on v2. (With an f32 value stream the staging is
+  // 4 B a lane narrower: 88 / 92 VGPRs, 5 waves/SIMD, so that one runs.)
+  if (rank == 8 && nother == 2 && sizeof(VS) == 8 && sizeof(S) == 8)
     return false;
-  const int phase = stream_phase<V>(key, idx, nother, vals);
+  const int phase = stream_phase<VS>(key, idx, nother, vals);
   if (phase < 0) return false;
   const int64_t quantum = 32 * (WAVE / rank);
   const int64_t span = pick_span(nnz) / quantum * quantum;
@@ -481,10 +487,10 @@ bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
               mats[0], mats[1], mats[2], mats[3], vals, nnz, span, phase, out
 #define L7(F_, N_) \
   if (rowptr) \
-    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, true>), grid, block, \
-                       0, st, ARGS7); \
+    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, true, VS>), grid, \
+                       block, 0, st, ARGS7); \
   else \
-    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, false>), grid, \
+    hipLaunchKernelGGL((mttkrp_flat7_kern<V, F_, N_, S, false, VS>), grid, \
                        block, 0, st, ARGS7)
 #define L7F(N_) \
   switch (rank) { case 8: L7(8, N_); break; case 16: L7(16, N_); break; \
@@ -910,6 +916,28 @@ extern "C" int splatt_hip_mttkrp_flat_rp_f64bf16(
                                     (const bf16 * const *)mats, vals, nnz,
                                     out, rank, nother,
                                     (hipStream_t)stream) ? 0 : -1;
+}
+
+// f32 value STREAM (f64 factors and accumulation) on the v7 kernel, row
+// pointers or key; `vals` is the 4-byte copy of f32-exact values. -1 =
+// declined (nothing launched): the caller runs the 8-byte stream.
+extern "C" int splatt_hip_mttkrp_flat_rp_f64v32(
+    const int64_t * rowptr, int64_t nrows, int64_t p0,
+    const int32_t * const * idx, const double * const * mats,
+    const float * vals, int64_t nnz, double * out, int rank, int nother,
+    void * stream) {
+  return launch_flat7<double, double, float>(
+             nullptr, rowptr, nrows, p0, idx, mats, vals, nnz, out, rank,
+             nother, (hipStream_t)stream) ? 0 : -1;
+}
+
+extern "C" int splatt_hip_mttkrp_flat_f64v32(
+    const int32_t * key, const int32_t * const * idx,
+    const double * const * mats, const float * vals, int64_t nnz,
+    double * out, int rank, int nother, void * stream) {
+  return launch_flat7<double, double, float>(
+             key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank, nother,
+             (hipStream_t)stream) ? 0 : -1;
 }
 
 // reduced-precision factor STORAGE (f64 accumulate) on the v7/v2 path;

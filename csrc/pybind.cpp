@@ -406,6 +406,13 @@ int splatt_hip_mttkrp_flat_rp_f64f32(
 int splatt_hip_mttkrp_flat_rp_f64bf16(
     const int64_t*, int64_t, int64_t, const int32_t* const*,
     const uint16_t* const*, const double*, int64_t, double*, int, int, void*);
+// f32 value stream (f64 factors/output), v7 only; -1 = declined
+int splatt_hip_mttkrp_flat_rp_f64v32(
+    const int64_t*, int64_t, int64_t, const int32_t* const*,
+    const double* const*, const float*, int64_t, double*, int, int, void*);
+int splatt_hip_mttkrp_flat_f64v32(
+    const int32_t*, const int32_t* const*, const double* const*,
+    const float*, int64_t, double*, int, int, void*);
 // deterministic flat kernel, csrc/hip/mttkrp_det.hip
 int64_t splatt_hip_flat_det_ws(int64_t, int);
 int splatt_hip_mttkrp_flat_det_f64(
@@ -743,6 +750,54 @@ static bool py_gpu_mttkrp_flat_rp(Tensor rowptr, int64_t p0,
   return splatt_hip_mttkrp_flat_rp_f32(
              rp, nrows, p0, ip, mp, vals.data_ptr<float>(), nnz,
              out.data_ptr<float>(), rank, nother, (void*)stream) == 0;
+}
+
+// f32 value stream of an f64 tensor (values all f32-exact, narrowed once by
+// the caller): the v7 kernel with row pointers (`rowptr` given) or the key
+// stream. Factors and output stay f64. Returns false when the launch does
+// not qualify for v7 — the caller then runs the 8-byte stream.
+static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
+                                   c10::optional<Tensor> key,
+                                   std::vector<Tensor> idx,
+                                   std::vector<Tensor> mats, Tensor vals32,
+                                   Tensor out, int64_t stream) {
+  const int nother = (int)idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
+  TORCH_CHECK((int)mats.size() == nother);
+  TORCH_CHECK(rowptr.has_value() != key.has_value(),
+              "pass row pointers or a key stream, not both");
+  TORCH_CHECK(vals32.is_cuda() && vals32.scalar_type() == torch::kFloat32
+              && vals32.is_contiguous(), "vals32 must be contiguous f32");
+  TORCH_CHECK(out.scalar_type() == torch::kFloat64 && out.is_contiguous(),
+              "out must be contiguous f64");
+  const int rank = (int)mats[0].size(1);
+  const int64_t nnz = vals32.numel();
+  const int32_t * ip[8] = {};
+  const double * mp[8] = {};
+  for (int t = 0; t < nother; ++t) {
+    TORCH_CHECK(idx[t].scalar_type() == torch::kInt32
+                && idx[t].numel() == nnz, "idx must be int32 of nnz entries");
+    TORCH_CHECK(mats[t].scalar_type() == torch::kFloat64
+                && mats[t].is_contiguous(), "factors must be contiguous f64");
+    ip[t] = idx[t].data_ptr<int32_t>();
+    mp[t] = mats[t].data_ptr<double>();
+  }
+  if (rowptr.has_value()) {
+    TORCH_CHECK(rowptr->scalar_type() == torch::kInt64
+                && rowptr->is_contiguous() && rowptr->numel() >= 2
+                && rowptr->numel() <= out.size(0) + 1,
+                "rowptr must be contiguous int64 with at most rows + 1 "
+                "entries");
+    return splatt_hip_mttkrp_flat_rp_f64v32(
+               rowptr->data_ptr<int64_t>(), rowptr->numel() - 1, p0, ip, mp,
+               vals32.data_ptr<float>(), nnz, out.data_ptr<double>(), rank,
+               nother, (void*)stream) == 0;
+  }
+  TORCH_CHECK(key->scalar_type() == torch::kInt32 && key->numel() == nnz,
+              "key must be int32 of nnz entries");
+  return splatt_hip_mttkrp_flat_f64v32(
+             key->data_ptr<int32_t>(), ip, mp, vals32.data_ptr<float>(), nnz,
+             out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
 }
 
 // deterministic flat MTTKRP (csrc/hip/mttkrp_det.hip): plain stores for
@@ -1084,7 +1139,96 @@ static void py_gpu_admm_update(Tensor K, Tensor Ginv, Tensor rho, Tensor H,
               splatt_hip_complete_errstr(rc));
 }
 
+// ------------------------------------------ fused dense ALS tail (f64 only)
+extern "C" {
+// csrc/hip/dense_kernels.hip, csrc/hip/als_tail.hip; positive return =
+// hipError_t of the launch, negative = the arguments do not qualify
+int splatt_hip_als_prep_f64(const double* const*, int, double, double*, int,
+                            double*, double*, double*, void*);
+int splatt_hip_als_tail_f64(const double*, const double*, int64_t, int,
+                            double*, double*, double*, double*, void*);
+int64_t splatt_hip_als_tail_cap_rows();
+}
+
+// One launch in front of the tail: Ginv = inverse of the Hadamard product
+// of `grams` (+ reg on the diagonal) — none: Ginv is left alone — and the
+// tail's accumulators reset: gram = 0, lam = 1, inner = 0 (when given).
+static void py_gpu_als_prep(std::vector<Tensor> grams, double reg,
+                            Tensor Ginv, Tensor gram, Tensor lam,
+                            c10::optional<Tensor> inner, int64_t stream) {
+  check_dev(Ginv, torch::kFloat64, "Ginv");
+  check_dev(gram, torch::kFloat64, "gram");
+  check_dev(lam, torch::kFloat64, "lam");
+  TORCH_CHECK(Ginv.dim() == 2 && Ginv.size(0) == Ginv.size(1),
+              "Ginv must be [rank, rank]");
+  const int F = (int)Ginv.size(0);
+  TORCH_CHECK(F >= 1 && F <= 64, "als_prep supports rank 1..64, got ", F);
+  TORCH_CHECK(grams.size() <= 8, "at most 8 Gram matrices");
+  TORCH_CHECK(gram.numel() == (int64_t)F * F && lam.numel() == F,
+              "gram must be [rank, rank] and lam [rank]");
+  const double * gp[8] = {};
+  for (size_t o = 0; o < grams.size(); ++o) {
+    check_dev(grams[o], torch::kFloat64, "grams");
+    TORCH_CHECK(grams[o].numel() == (int64_t)F * F,
+                "every Gram must be [rank, rank]");
+    TORCH_CHECK(grams[o].data_ptr() != gram.data_ptr(),
+                "the Gram being reset cannot be an input");
+    gp[o] = grams[o].data_ptr<double>();
+  }
+  double * ip = nullptr;
+  if (inner.has_value()) {
+    check_dev(*inner, torch::kFloat64, "inner");
+    TORCH_CHECK(inner->numel() == F, "inner must be [rank]");
+    ip = inner->data_ptr<double>();
+  }
+  const int rc = splatt_hip_als_prep_f64(
+      gp, (int)grams.size(), reg, Ginv.data_ptr<double>(), F,
+      gram.data_ptr<double>(), lam.data_ptr<double>(), ip, (void*)stream);
+  TORCH_CHECK(rc == 0, "als_prep kernel launch failed: ",
+              rc > 0 ? splatt_hip_complete_errstr(rc) : "bad arguments");
+}
+
+// The two passes of the tail. lam, gram and inner accumulate: they must
+// have been reset by gpu_als_prep on the same stream.
+static void py_gpu_als_tail(Tensor K, Tensor Ginv, Tensor A, Tensor lam,
+                            Tensor gram, c10::optional<Tensor> inner,
+                            int64_t stream) {
+  check_dev(K, torch::kFloat64, "K");
+  check_dev(Ginv, torch::kFloat64, "Ginv");
+  check_dev(A, torch::kFloat64, "A");
+  check_dev(lam, torch::kFloat64, "lam");
+  check_dev(gram, torch::kFloat64, "gram");
+  TORCH_CHECK(K.dim() == 2 && K.sizes() == A.sizes(),
+              "K and A must be [rows, rank] of one shape");
+  const int64_t n = K.size(0);
+  const int F = (int)K.size(1);
+  TORCH_CHECK(F == 16 || F == 32 || F == 64,
+              "the fused tail exists for ranks 16, 32 and 64, got ", F);
+  TORCH_CHECK(Ginv.numel() == (int64_t)F * F && gram.numel() == (int64_t)F * F
+              && lam.numel() == F, "Ginv/gram must be [rank, rank], lam [rank]");
+  TORCH_CHECK(K.data_ptr() != A.data_ptr(), "K and A must not alias");
+  double * ip = nullptr;
+  if (inner.has_value()) {
+    check_dev(*inner, torch::kFloat64, "inner");
+    TORCH_CHECK(inner->numel() == F, "inner must be [rank]");
+    ip = inner->data_ptr<double>();
+  }
+  const int rc = splatt_hip_als_tail_f64(
+      K.data_ptr<double>(), Ginv.data_ptr<double>(), n, F,
+      A.data_ptr<double>(), lam.data_ptr<double>(), gram.data_ptr<double>(),
+      ip, (void*)stream);
+  TORCH_CHECK(rc == 0, "als_tail kernel launch failed: ",
+              rc > 0 ? splatt_hip_complete_errstr(rc)
+                     : "rank or alignment does not qualify");
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("gpu_als_prep", &py_gpu_als_prep,
+        "Hadamard of Grams + SPD inverse + reset of the tail accumulators");
+  m.def("gpu_als_tail", &py_gpu_als_tail,
+        "fused ALS tail: A = (K Ginv)/lam, lam, gram += A^T A, inner");
+  m.def("als_tail_cap_rows", &splatt_hip_als_tail_cap_rows,
+        "row count at which the fused tail's grid reaches its cap");
   m.def("gpu_admm_update", &py_gpu_admm_update,
         "fused block-ADMM factor update (in place on H, U)");
   m.def("gpu_ttmc", &py_gpu_ttmc,
@@ -1113,6 +1257,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_mttkrp_flat_rp", &py_gpu_mttkrp_flat_rp,
         "flat MTTKRP with row pointers in place of the key stream (root "
         "output, key-sorted stream); false = declined, use gpu_mttkrp_flat");
+  m.def("gpu_mttkrp_flat_v32", &py_gpu_mttkrp_flat_v32,
+        "flat MTTKRP (v7) reading an f32 copy of f32-exact f64 values, by "
+        "row pointers or key stream; false = declined, use the f64 stream");
   m.def("gpu_mttkrp_flat_det", &py_gpu_mttkrp_flat_det,
         "bitwise-deterministic flat MTTKRP (depth-0 streams, spec ranks)");
   m.def("flat_det_ws_elems", &splatt_hip_flat_det_ws,

@@ -22,7 +22,8 @@ import torch
 from splatt_amd._ext import native
 from splatt_amd.csf import CsfSet, csf_alloc
 from splatt_amd.mttkrp import mttkrp
-from splatt_amd.ops.dense import gram, solve_rows, spd_inverse
+from splatt_amd.ops.dense import (als_tail, fused_tail_ok, gram, solve_rows,
+                                  spd_inverse)
 from splatt_amd.sptensor import SpTensor
 
 
@@ -120,6 +121,15 @@ def cpd_als(src: CsfSet | SpTensor, rank: int,
             fit = old_fit = float(ck["fit"])
             trace = list(ck.get("fit_trace", []))
 
+    # steady-state iterations on device at ranks 16/32/64 (f64) take the
+    # fused dense tail (ops.dense.als_tail): Hadamard + inverse, solve,
+    # max-norm, Gram and the fit's inner products in three launches
+    fused = fused_tail_ok(rank, dtype, dev)
+    if fused:
+        Ginv_buf = torch.empty(rank, rank, dtype=dtype, device=dev)
+        inner_buf = torch.zeros(rank, dtype=dtype, device=dev)
+    inner_fused = False
+
     import time as _time
     for it in range(it0, opts.max_iters):
         _t0 = _time.perf_counter()
@@ -127,6 +137,21 @@ def cpd_als(src: CsfSet | SpTensor, rank: int,
             mb = buf[: dims[m]]
             mttkrp(cs, qfactors or factors, m, out=mb,
                    nthreads=opts.nthreads)
+            if fused and it >= 1:
+                A = torch.empty_like(mb)
+                lam = torch.empty(rank, dtype=dtype, device=dev)
+                # grams[m] is not an input of its own update: reset and
+                # refilled in place
+                als_tail(mb, Ginv_buf, A, lam, grams[m],
+                         inner=inner_buf if m == nm - 1 else None,
+                         grams=[grams[o] for o in range(nm) if o != m],
+                         reg=float(opts.regularize))
+                inner_fused = True
+                factors[m] = A
+                if qfactors is not None:
+                    qfactors[m] = A.to(qdt)
+                continue
+            inner_fused = False
             G = ones.clone()
             for o in range(nm):
                 if o != m:
@@ -147,9 +172,12 @@ def cpd_als(src: CsfSet | SpTensor, rank: int,
         # fit from last mode's pre-solve MTTKRP output (reference trick):
         # <X,K> = sum_f lam_f * sum_i buf[i,f] * A_last[i,f]
         mlast = nm - 1
-        inner = float(((buf[: dims[mlast]].double()
-                        * factors[mlast].double()).sum(dim=0)
-                       * lam.double()).sum())
+        if inner_fused:
+            inner = float((inner_buf * lam).sum())
+        else:
+            inner = float(((buf[: dims[mlast]].double()
+                            * factors[mlast].double()).sum(dim=0)
+                           * lam.double()).sum())
         Gall = ones.clone()
         for o in range(nm):
             Gall *= grams[o]

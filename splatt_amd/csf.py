@@ -86,6 +86,12 @@ class Csf:
         rowptr = getattr(self, "_rowptr", None)
         if rowptr is not None:
             object.__setattr__(c, "_rowptr", rowptr.to(device))
+        # f32 value stream of the flat kernel (mttkrp.py _vals32): the
+        # copy, or False when the values are not all f32-exact
+        v32 = getattr(self, "_vals32", None)
+        if v32 is not None:
+            object.__setattr__(c, "_vals32",
+                               v32 if v32 is False else v32.to(device))
         return c
 
     def storage_bytes(self) -> int:
@@ -93,6 +99,9 @@ class Csf:
         rowptr = getattr(self, "_rowptr", None)
         if rowptr is not None:
             b += rowptr.numel() * rowptr.element_size()
+        v32 = getattr(self, "_vals32", None)
+        if v32 is not None and v32 is not False:
+            b += v32.numel() * v32.element_size()
         pack = getattr(self, "_pack", None)
         if pack is not None:
             # expansions/leaf fids are strided views into the pack

@@ -182,6 +182,41 @@ def _root_rowptr(c: Csf) -> torch.Tensor:
     return rp
 
 
+_VALS32_CHUNK = 1 << 26     # elements compared per step of the exactness check
+
+
+def _vals32(c: Csf, rank: int, mats: List[torch.Tensor]):
+    """f32 copy of the values for the unstaged v7 dispatch, or None.
+
+    The values of a tensor do not change during a decomposition; when every
+    one of them is exactly representable in f32 (ratings, counts, data that
+    was f32 to begin with), a 4-byte stream carries the same information and
+    the kernel widens each value on load. Checked once per Csf, on the first
+    eligible dispatch outside stream capture, and cached next to the row
+    pointers: the f32 copy, or False. Eligible: f64 values and factors,
+    unstaged build, a rank and mode count the v7 kernel takes (the launcher
+    may still decline, and the dispatch then reads the f64 stream).
+    SPLATT_VALS32=0 disables it. Costs 4 B/nnz per CSF."""
+    if os.environ.get("SPLATT_VALS32") == "0":
+        return None
+    if (c.vals.dtype != torch.float64 or mats[0].dtype != torch.float64
+            or getattr(c, "_stage", None) is not None
+            or rank not in (8, 16, 32, 64) or not 3 <= c.nmodes <= 5):
+        return None
+    v = getattr(c, "_vals32", None)
+    if v is None:
+        if torch.cuda.is_current_stream_capturing():
+            return None           # no answer yet: the wide stream
+        v = c.vals.float()
+        for s in range(0, c.nnz, _VALS32_CHUNK):
+            if not torch.equal(v[s: s + _VALS32_CHUNK].double(),
+                               c.vals[s: s + _VALS32_CHUNK]):
+                v = False
+                break
+        object.__setattr__(c, "_vals32", v)
+    return None if v is False else v
+
+
 def _gpu_mttkrp_det(c: Csf, depth: int, mats: List[torch.Tensor],
                     out: torch.Tensor) -> None:
     """Bitwise-deterministic device MTTKRP (csrc/hip/mttkrp_det.hip):
@@ -335,6 +370,16 @@ def _gpu_mttkrp_flat(c: Csf, depth: int, mats: List[torch.Tensor],
             continue
         idx.append(c.ancestor_expand(l)[p0:p1].contiguous())
         ms.append(mats[c.dim_perm[l]].contiguous())
+    v32 = _vals32(c, rank, mats)
+    if v32 is not None:
+        # rows-restricted launches slice the copy exactly as they slice vals
+        if flat_rowptr_ok(c, depth, rank):
+            if native().gpu_mttkrp_flat_v32(_root_rowptr(c), p0, None, idx,
+                                            ms, v32[p0:p1], out, stream):
+                return
+        elif native().gpu_mttkrp_flat_v32(None, 0, key[p0:p1].contiguous(),
+                                          idx, ms, v32[p0:p1], out, stream):
+            return
     if flat_rowptr_ok(c, depth, rank) and native().gpu_mttkrp_flat_rp(
             _root_rowptr(c), p0, idx, ms, c.vals[p0:p1], out, stream):
         return

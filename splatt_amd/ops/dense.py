@@ -55,6 +55,38 @@ def spd_inverse(G: torch.Tensor) -> torch.Tensor:
     return torch.linalg.pinv(G)
 
 
+def fused_tail_ok(F: int, dtype: torch.dtype, device: torch.device) -> bool:
+    """Does the steady-state (max-norm) mode update take the fused tail
+    kernels? f64 on device at ranks 16/32/64; SPLATT_DETERMINISTIC=1 and
+    SPLATT_FUSED_TAIL=0 keep the library chain."""
+    import os
+    return (device.type == "cuda" and dtype == torch.float64
+            and F in (16, 32, 64)
+            and os.environ.get("SPLATT_DETERMINISTIC") != "1"
+            and os.environ.get("SPLATT_FUSED_TAIL") != "0")
+
+
+def als_tail(K: torch.Tensor, Ginv: torch.Tensor, A: torch.Tensor,
+             lam: torch.Tensor, gram_out: torch.Tensor,
+             inner: torch.Tensor | None = None,
+             grams: list | None = None, reg: float = 0.0) -> None:
+    """Fused dense tail of one ALS mode update (csrc/hip/als_tail.hip):
+
+        T = K @ Ginv ; lam = max(1, max_i |T|) ; A = T / lam
+        gram_out = A^T A ; inner[f] = sum_i K[i,f] A[i,f]   (if given)
+
+    Three launches on the current stream, all outputs written into the
+    caller's (static) buffers, no host sync: capture-safe and replayable.
+    With `grams` (the other modes' Gram matrices, none of them gram_out)
+    the first launch also forms Ginv = inv(hadamard(grams) + reg*I);
+    without, Ginv is an input. That launch resets lam, gram_out and inner,
+    so calling again on the same buffers does not accumulate."""
+    stream = torch.cuda.current_stream().cuda_stream
+    native().gpu_als_prep(list(grams) if grams is not None else [], reg,
+                          Ginv, gram_out, lam, inner, stream)
+    native().gpu_als_tail(K, Ginv, A, lam, gram_out, inner, stream)
+
+
 def solve_rows(mb: torch.Tensor, Ginv: torch.Tensor) -> torch.Tensor:
     """mb @ Ginv — the CPD solve GEMM. Default: library GEMM. With
     SPLATT_DETERMINISTIC=1 on device (F in the spec set): the one-thread-

@@ -8,6 +8,10 @@ iteration into a hipGraph (torch.cuda.CUDAGraph on ROCm); replay then
 costs one launch. The fit is accumulated on device and only read back
 after the timed region. Max-norm (it>=1) schedule only — iteration 0 runs
 eager. Falls back to the eager step if capture fails.
+
+For f64 at ranks 16/32/64 (non-deterministic) the dense tail of a mode is
+the fused one (ops.dense.als_tail, csrc/hip/als_tail.hip): three launches
+and three passes over the n x F arrays instead of the library chain below.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ import torch
 
 from splatt_amd.mttkrp import mttkrp
 from splatt_amd._ext import native
+from splatt_amd.ops.dense import als_tail, fused_tail_ok
 
 
 class GraphStepRunner:
@@ -45,7 +50,6 @@ class GraphStepRunner:
         self.lam.copy_(st.lam)
         self.fit_parts = torch.zeros(2, dtype=torch.float64, device=dev)
         self.buf = st.buf
-        self.tmp = torch.empty_like(st.buf)
         # deterministic mode: static workspaces for the atomic-free
         # solve/gram kernels (mttkrp already reads the env per call)
         import os
@@ -57,6 +61,14 @@ class GraphStepRunner:
                 nparts = max(1, min(256, (dec.chunkn[m] + 63) // 64))
                 self.gpart.append(torch.empty(nparts * F * F, dtype=dtype,
                                               device=dev))
+        # fused dense tail (f64, ranks 16/32/64): the fit's inner products
+        # come out of the last mode's tail, so the n x F product buffer of
+        # the library chain is not needed
+        self.fused = not self.det and fused_tail_ok(F, dtype, dev)
+        if self.fused:
+            self.inner = torch.zeros(F, dtype=dtype, device=dev)
+        else:
+            self.tmp = torch.empty_like(st.buf)
 
     def _static_step(self):
         st, nm = self.st, self.nm
@@ -67,6 +79,14 @@ class GraphStepRunner:
             mb = self.buf[:n]
             mttkrp(st.cs, self.A, m, out=mb)
             # G = hadamard of other grams (+jitter), L = chol, Ginv
+            if self.fused:
+                # Hadamard + inverse + accumulator reset, then the two
+                # passes of the fused tail; the last mode also leaves
+                # inner[f] = sum_i K[i,f] A[i,f] for the fit
+                als_tail(mb, self.Ginv, self.A[m], self.lam, self.grams[m],
+                         inner=self.inner if m == nm - 1 else None,
+                         grams=[self.grams[o] for o in range(nm) if o != m])
+                continue
             first = True
             for o in range(nm):
                 if o == m:
@@ -94,10 +114,14 @@ class GraphStepRunner:
         # fit parts on device: [inner, knorm]
         mlast = nm - 1
         n = dec.chunkn[mlast]
-        t = self.tmp[:n]
-        torch.mul(self.buf[:n], self.A[mlast], out=t)
-        inner_cols = t.sum(dim=0)          # small alloc (F) — capture-safe
-        self.fit_parts[0] = (inner_cols.double() * self.lam.double()).sum()
+        if self.fused:
+            self.fit_parts[0] = (self.inner * self.lam).sum()
+        else:
+            t = self.tmp[:n]
+            torch.mul(self.buf[:n], self.A[mlast], out=t)
+            inner_cols = t.sum(dim=0)      # small alloc (F) — capture-safe
+            self.fit_parts[0] = (inner_cols.double()
+                                 * self.lam.double()).sum()
         first = True
         for o in range(nm):
             if first:
