@@ -20,22 +20,7 @@
 #include "../core/csf.hpp"
 #include "../core/cpd.hpp"
 #include "../core/matrix.hpp"
-
-extern "C" {
-void splatt_hip_mttkrp_flat_f64(
-    const int32_t * key, const int32_t * const * idx,
-    const double * const * mats, const double * vals, int64_t nnz,
-    double * out, int rank, int nother, void * stream);
-int splatt_hip_rowsolve_f64(const double *, const double *, double *,
-                            int64_t, int, void *);
-void splatt_hip_gram_f64(const double *, int64_t, int, double *, void *);
-void splatt_hip_spd_inverse_f64(const double *, double *, int, void *);
-void splatt_hip_colacc_f64(const double *, int64_t, int, int, double *,
-                           void *);
-void splatt_hip_colscale_f64(double *, int64_t, int, const double *, void *);
-void splatt_hip_coldot_f64(const double *, const double *, int64_t, int,
-                           double *, void *);
-}
+#include "../hip/launchers.hpp"
 
 namespace splatt {
 
@@ -45,6 +30,12 @@ void hip_check(hipError_t e, const char * what) {
   if (e != hipSuccess)
     throw std::runtime_error(std::string(what) + ": " +
                              hipGetErrorString(e));
+}
+
+// a launcher's return value (csrc/hip/launchers.hpp): 0 or a hipError_t for
+// the ones used here, which never decline
+void launch_check(int rc, const char * what) {
+  hip_check((hipError_t)rc, what);
 }
 
 template <typename T>
@@ -181,9 +172,10 @@ int mttkrp_gpu<double>(const CsfSet<double> & set, void ** cache_slot,
     matp[t] = dmats[c.dim_perm[l]].p;
     ++t;
   }
-  splatt_hip_mttkrp_flat_f64(cache->labs[ci][depth].p, idxp, matp,
-                             cache->vals[ci].p, (int64_t)c.nnz, dout.p,
-                             rank, nm - 1, st);
+  launch_check(hip::mttkrp_flat<double>(
+                   cache->labs[ci][depth].p, nullptr, 0, 0, idxp, matp,
+                   cache->vals[ci].p, (int64_t)c.nnz, dout.p, rank, nm - 1,
+                   st), "mttkrp");
   hip_check(hipStreamSynchronize(st), "sync");
   hip_check(hipMemcpy(out_host, dout.p,
                       sizeof(double) * c0.dims[mode] * rank,
@@ -275,8 +267,10 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
         matp[t] = dA[c.dim_perm[l]].p;
         ++t;
       }
-      splatt_hip_mttkrp_flat_f64(labs[ci][depth].p, idxp, matp, dvals[ci].p,
-                                 (int64_t)c.nnz, dbuf.p, F, nm - 1, st);
+      launch_check(hip::mttkrp_flat<double>(
+                       labs[ci][depth].p, nullptr, 0, 0, idxp, matp,
+                       dvals[ci].p, (int64_t)c.nnz, dbuf.p, F, nm - 1, st),
+                   "mttkrp");
       // normal equations: G = hadamard of other grams (+reg I)
       std::array<const double*, MAX_NMODES> gp{};
       for (int o = 0; o < nm; ++o) gp[o] = grams[o].data();
@@ -287,9 +281,10 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
       if (spec) {
         hip_check(hipMemcpyAsync(dG.p, G.data(), sizeof(double) * F * F,
                                  hipMemcpyHostToDevice, st), "G H2D");
-        splatt_hip_spd_inverse_f64(dG.p, dGinv.p, F, st);
-        if (splatt_hip_rowsolve_f64(dbuf.p, dGinv.p, dA[m].p, (int64_t)n,
-                                    F, st) != 0)
+        launch_check(hip::spd_inverse<double>(dG.p, dGinv.p, F, st),
+                     "spd_inverse");
+        if (hip::rowsolve<double>(dbuf.p, dGinv.p, dA[m].p, (int64_t)n, F,
+                                  st) != 0)
           throw std::runtime_error("rowsolve failed");
       } else {
         // generic rank: Cholesky solve on host (small F, n-row RHS)
@@ -306,8 +301,8 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
       // cpd.c:343-347); lambda math on host (length F)
       hip_check(hipMemsetAsync(dsmall.p, 0, sizeof(double) * F, st),
                 "memset");
-      splatt_hip_colacc_f64(dA[m].p, (int64_t)n, F, it == 0 ? 0 : 1,
-                            dsmall.p, st);
+      launch_check(hip::colacc(dA[m].p, (int64_t)n, F, it == 0 ? 0 : 1,
+                               dsmall.p, st), "colacc");
       hip_check(hipStreamSynchronize(st), "sync");
       hip_check(hipMemcpy(lamh.data(), dsmall.p, sizeof(double) * F,
                           hipMemcpyDeviceToHost), "lam D2H");
@@ -319,11 +314,13 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
       }
       hip_check(hipMemcpyAsync(dsmall.p, lamh.data(), sizeof(double) * F,
                                hipMemcpyHostToDevice, st), "lam H2D");
-      splatt_hip_colscale_f64(dA[m].p, (int64_t)n, F, dsmall.p, st);
+      launch_check(hip::colscale(dA[m].p, (int64_t)n, F, dsmall.p, st),
+                   "colscale");
       // fresh Gram of the updated factor
       hip_check(hipMemsetAsync(dG.p, 0, sizeof(double) * F * F, st),
                 "memset");
-      splatt_hip_gram_f64(dA[m].p, (int64_t)n, F, dG.p, st);
+      launch_check(hip::gram<double>(dA[m].p, (int64_t)n, F, dG.p, st),
+                   "gram");
       hip_check(hipStreamSynchronize(st), "sync");
       hip_check(hipMemcpy(grams[m].data(), dG.p, sizeof(double) * F * F,
                           hipMemcpyDeviceToHost), "gram D2H");
@@ -332,8 +329,8 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
     // fit: inner product from the last mode's pre-solve MTTKRP output
     const int lastm = nm - 1;
     hip_check(hipMemsetAsync(dsmall.p, 0, sizeof(double) * F, st), "memset");
-    splatt_hip_coldot_f64(dbuf.p, dA[lastm].p, (int64_t)c0.dims[lastm], F,
-                          dsmall.p, st);
+    launch_check(hip::coldot(dbuf.p, dA[lastm].p, (int64_t)c0.dims[lastm],
+                             F, dsmall.p, st), "coldot");
     hip_check(hipStreamSynchronize(st), "sync");
     hip_check(hipMemcpy(lamh.data(), dsmall.p, sizeof(double) * F,
                         hipMemcpyDeviceToHost), "inner D2H");
@@ -359,7 +356,8 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
   for (int m = 0; m < nm; ++m) {
     const idx_t n = c0.dims[m];
     hip_check(hipMemsetAsync(dsmall.p, 0, sizeof(double) * F, st), "memset");
-    splatt_hip_colacc_f64(dA[m].p, (int64_t)n, F, 0, dsmall.p, st);
+    launch_check(hip::colacc(dA[m].p, (int64_t)n, F, 0, dsmall.p, st),
+                 "colacc");
     hip_check(hipStreamSynchronize(st), "sync");
     hip_check(hipMemcpy(lamh.data(), dsmall.p, sizeof(double) * F,
                         hipMemcpyDeviceToHost), "norm D2H");
@@ -370,7 +368,8 @@ Kruskal<double> cpd_als_gpu<double>(const CsfSet<double> & set, int rank,
     }
     hip_check(hipMemcpyAsync(dsmall.p, lamh.data(), sizeof(double) * F,
                              hipMemcpyHostToDevice, st), "norm H2D");
-    splatt_hip_colscale_f64(dA[m].p, (int64_t)n, F, dsmall.p, st);
+    launch_check(hip::colscale(dA[m].p, (int64_t)n, F, dsmall.p, st),
+                 "colscale");
     hip_check(hipStreamSynchronize(st), "sync");
     hip_check(hipMemcpy(k.factors[m].data(), dA[m].p,
                         sizeof(double) * n * F, hipMemcpyDeviceToHost),

@@ -29,11 +29,12 @@
 // thread 0): no atomics, so the update is bitwise reproducible.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "mfma_acc.hpp"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int NT = 256;
 constexpr int BLOCK_ROWS = 64;
 
@@ -245,18 +246,18 @@ int launch(const double * K, const double * Ginv, const double * rho,
   hipLaunchKernelGGL((admm_block_kern<FC, J, MFMA>), dim3((uint32_t)nblocks),
                      dim3(NT), lds, st, K, Ginv, rho, H, U, iters, n, F, kind,
                      w, lo, hi, inner_tol, max_inner);
-  return (int)hipGetLastError();
+  return launch_rc();
 }
 
 }  // namespace
 
-// variant: 0 = the default instance for this rank, 1 = VALU, 2 = MFMA
-// (ranks 16/32/64 only). Nonzero return = hipError_t.
-extern "C" int splatt_hip_admm_update_f64(
-    const double * K, const double * Ginv, const double * rho, double * H,
-    double * U, int32_t * iters, int64_t n, int F, int kind, double w,
-    double lo, double hi, double inner_tol, int max_inner, int variant,
-    void * stream) {
+namespace splatt {
+namespace hip {
+
+int admm_update(const double * K, const double * Ginv, const double * rho,
+                double * H, double * U, int32_t * iters, int64_t n, int F,
+                int kind, double w, double lo, double hi, double inner_tol,
+                int max_inner, int variant, void * stream) {
   if (n <= 0) return 0;
   const bool spec = F == 16 || F == 32 || F == 64;
   if (F < 1 || F > 64 || kind < 0 || kind > 3 || max_inner < 0
@@ -281,3 +282,6 @@ extern "C" int splatt_hip_admm_update_f64(
   return launch<0, 16, false>(AARGS);
 #undef AARGS
 }
+
+}  // namespace hip
+}  // namespace splatt

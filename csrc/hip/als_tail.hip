@@ -23,7 +23,7 @@
 // and rescaling it in place would cost a fourth pass over memory.
 //
 // lam, gram and inner must hold 1, 0 and 0 when pass 1 starts: the
-// Hadamard + inverse launch in front (splatt_hip_als_prep_f64,
+// Hadamard + inverse launch in front (splatt::hip::als_prep,
 // dense_kernels.hip) resets them, so there is no memset launch.
 //
 // Layout. A wave owns 16 rows per step; T = K * Ginv is a plain (not
@@ -45,11 +45,12 @@
 // maxima through LDS; one atomic per element per block reaches memory.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "mfma_acc.hpp"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int NT = 256;
 constexpr int WPB = NT / WAVE;
 constexpr int TILE = 16;         // rows per wave step
@@ -306,24 +307,20 @@ int launch_tail(const double * K, const double * Ginv, int64_t n, double * A,
   else
     hipLaunchKernelGGL((tail_scale_kern<F, false>), grid, block, 0, st, K,
                        Ginv, lam, n, A, gram, inner);
-  return (int)hipGetLastError();
+  return launch_rc();
 }
 
 }  // namespace
 
-// Launch-row count at which the grid reaches its cap (tests cover it).
-extern "C" int64_t splatt_hip_als_tail_cap_rows() {
-  return (int64_t)MAX_BLOCKS * WPB * TILE;
-}
+namespace splatt {
+namespace hip {
 
-// lam (F), gram (F x F) and inner (F, may be null) must have been reset to
-// 1 / 0 / 0 on this stream (splatt_hip_als_prep_f64). K, A 16-B aligned,
-// row-major, not aliased. Returns the launch status (0 = ok), -1 for a
-// rank outside 16/32/64, -2 for a misaligned pointer.
-extern "C" int splatt_hip_als_tail_f64(const double * K, const double * Ginv,
-                                       int64_t n, int F, double * A,
-                                       double * lam, double * gram,
-                                       double * inner, void * stream) {
+// (tests cover launches past the cap)
+int64_t als_tail_cap_rows() { return (int64_t)MAX_BLOCKS * WPB * TILE; }
+
+int als_tail(const double * K, const double * Ginv, int64_t n, int F,
+             double * A, double * lam, double * gram, double * inner,
+             void * stream) {
   if (((uintptr_t)K | (uintptr_t)A) & 15) return -2;
   if (n <= 0) return (F == 16 || F == 32 || F == 64) ? 0 : -1;
   hipStream_t st = (hipStream_t)stream;
@@ -334,3 +331,6 @@ extern "C" int splatt_hip_als_tail_f64(const double * K, const double * Ginv,
     default: return -1;
   }
 }
+
+}  // namespace hip
+}  // namespace splatt

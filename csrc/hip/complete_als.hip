@@ -23,11 +23,12 @@
 // With reg > 0 every system is SPD: no jitter escalation.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "mfma_acc.hpp"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int TR = 32;  // nonzeros staged per LDS tile (generic kernel)
 
 // other-mode index streams + factors, BY VALUE in the kernel-arg block
@@ -377,8 +378,6 @@ int check_lds(size_t bytes) {
   return bytes <= (size_t)lim ? 0 : (int)hipErrorInvalidValue;
 }
 
-int launch_rc() { return (int)hipGetLastError(); }
-
 template <int F>
 int launch_mfma(const CmplTab & tab, int nother, const double * vals,
                 const int64_t * seg_start, const int32_t * seg_len,
@@ -404,22 +403,18 @@ int launch_mfma(const CmplTab & tab, int nother, const double * vals,
 
 }  // namespace
 
-extern "C" int64_t splatt_hip_complete_slot_elems(int F) {
-  return slot_elems(F);
-}
+namespace splatt {
+namespace hip {
 
-extern "C" const char * splatt_hip_complete_errstr(int rc) {
-  return hipGetErrorString((hipError_t)rc);
-}
+int64_t complete_slot_elems(int F) { return slot_elems(F); }
 
-// segments [seg0, seg0+nseg) of one output mode; slots of this launch are
-// seg_slot - slot0 (>= 0 for multi-segment rows, seg_slot < 0 otherwise)
-extern "C" int splatt_hip_complete_segments_f64(
-    const int32_t * const * idx, const double * const * mats, int nother,
-    const double * vals, const int64_t * seg_start, const int32_t * seg_len,
-    const int32_t * seg_row, const int32_t * seg_slot, int64_t seg0,
-    int64_t nseg, int64_t slot0, int F, double reg, double * ws,
-    double * out, void * stream) {
+int complete_segments(const int32_t * const * idx,
+                      const double * const * mats, int nother,
+                      const double * vals, const int64_t * seg_start,
+                      const int32_t * seg_len, const int32_t * seg_row,
+                      const int32_t * seg_slot, int64_t seg0, int64_t nseg,
+                      int64_t slot0, int F, double reg, double * ws,
+                      double * out, void * stream) {
   if (nseg <= 0) return 0;
   if (F < 1 || F > 64 || nother < 2 || nother > 7 || nseg > 0x7FFFFFFF)
     return (int)hipErrorInvalidValue;
@@ -449,12 +444,10 @@ extern "C" int splatt_hip_complete_segments_f64(
   return launch_rc();
 }
 
-// multi-segment rows [m0, m0+nm): fold slots mslot[m]..mslot[m+1] (minus
-// slot0) and solve
-extern "C" int splatt_hip_complete_reduce_f64(
-    const double * ws, const int32_t * mrow, const int64_t * mslot,
-    int64_t m0, int64_t nm, int64_t slot0, int F, double reg, double * out,
-    void * stream) {
+int complete_reduce(const double * ws, const int32_t * mrow,
+                    const int64_t * mslot, int64_t m0, int64_t nm,
+                    int64_t slot0, int F, double reg, double * out,
+                    void * stream) {
   if (nm <= 0) return 0;
   if (F < 1 || F > 64 || nm > 0x7FFFFFFF) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
@@ -472,9 +465,9 @@ extern "C" int splatt_hip_complete_reduce_f64(
   return launch_rc();
 }
 
-extern "C" int splatt_hip_kruskal_predict_f64(
-    const int64_t * const * inds, const double * const * mats, int nmodes,
-    const double * lam, int64_t n, int F, double * out, void * stream) {
+int kruskal_predict(const int64_t * const * inds, const double * const * mats,
+                    int nmodes, const double * lam, int64_t n, int F,
+                    double * out, void * stream) {
   if (n <= 0) return 0;
   if (F < 1 || nmodes < 1 || nmodes > 8) return (int)hipErrorInvalidValue;
   PredTab tab{};
@@ -487,3 +480,6 @@ extern "C" int splatt_hip_kruskal_predict_f64(
                      0, (hipStream_t)stream, tab, nmodes, lam, n, F, W, out);
   return launch_rc();
 }
+
+}  // namespace hip
+}  // namespace splatt

@@ -9,17 +9,14 @@
 // Capability parity: reference mat_aTa (src/matrix.c:414-455).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "mfma_acc.hpp"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int TR = 32;  // rows staged per LDS tile
-
-template <typename V>
-__device__ __forceinline__ void atomic_add_g(V * p, V v) {
-  unsafeAtomicAdd(p, v);
-}
 
 template <typename V, int PAIRS>
 __global__ void __launch_bounds__(TPB)
@@ -329,49 +326,8 @@ gram_det_fold_kern(const V * __restrict__ Gpart, int64_t nparts, int F,
   }
 }
 
-template <typename V>
-int launch_rowsolve(const V * A, const V * B, V * C, int64_t n, int F,
-                    hipStream_t st) {
-  const int rows_pb = 256 / (F < 256 ? F : 256);
-  int64_t blocks = (n + rows_pb - 1) / rows_pb;
-  if (blocks > 8192) blocks = 8192;          // grid-stride beyond this
-  if (blocks < 1) blocks = 1;
-  dim3 g((uint32_t)blocks), b(256);
-  switch (F) {
-    case 4:  hipLaunchKernelGGL((rowsolve_kern<V, 4>),  g, b, 0, st, A, B, C, n); return 0;
-    case 8:  hipLaunchKernelGGL((rowsolve_kern<V, 8>),  g, b, 0, st, A, B, C, n); return 0;
-    case 16: hipLaunchKernelGGL((rowsolve_kern<V, 16>), g, b, 0, st, A, B, C, n); return 0;
-    case 32: hipLaunchKernelGGL((rowsolve_kern<V, 32>), g, b, 0, st, A, B, C, n); return 0;
-    case 64: hipLaunchKernelGGL((rowsolve_kern<V, 64>), g, b, 0, st, A, B, C, n); return 0;
-    default: return -1;
-  }
-}
-
-}  // namespace
-
-extern "C" void splatt_hip_gram_det_f64(const double * A, int64_t n, int F,
-                                        double * Gpart, int64_t nparts,
-                                        double * G, void * stream) {
-  const int64_t rpb = (n + nparts - 1) / nparts;
-  hipLaunchKernelGGL((gram_det_part_kern<double>), dim3((uint32_t)nparts),
-                     dim3(256), 0, (hipStream_t)stream, A, n, F, rpb, Gpart);
-  hipLaunchKernelGGL((gram_det_fold_kern<double>), dim3(1), dim3(256), 0,
-                     (hipStream_t)stream, Gpart, nparts, F, G);
-}
-extern "C" void splatt_hip_gram_det_f32(const float * A, int64_t n, int F,
-                                        float * Gpart, int64_t nparts,
-                                        float * G, void * stream) {
-  const int64_t rpb = (n + nparts - 1) / nparts;
-  hipLaunchKernelGGL((gram_det_part_kern<float>), dim3((uint32_t)nparts),
-                     dim3(256), 0, (hipStream_t)stream, A, n, F, rpb, Gpart);
-  hipLaunchKernelGGL((gram_det_fold_kern<float>), dim3(1), dim3(256), 0,
-                     (hipStream_t)stream, Gpart, nparts, F, G);
-}
-
 // ---- generic column reductions/scales for the torch-free C API device
 // driver (csrc/capi/capi_gpu.cpp): F <= 64, one lane group per column.
-namespace {
-
 __device__ inline void atomic_max_f64(double * p, double v) {
   unsigned long long * u = reinterpret_cast<unsigned long long *>(p);
   unsigned long long old = *u, assumed;
@@ -430,71 +386,94 @@ coldot_kern(const double * __restrict__ X, const double * __restrict__ A,
 
 }  // namespace
 
-extern "C" void splatt_hip_colacc_f64(const double * A, int64_t n, int F,
-                                      int which, double * out,
-                                      void * stream) {
+namespace splatt {
+namespace hip {
+
+template <typename V>
+int gram_det(const V * A, int64_t n, int F, V * Gpart, int64_t nparts, V * G,
+             void * stream) {
+  const int64_t rpb = (n + nparts - 1) / nparts;
+  hipLaunchKernelGGL((gram_det_part_kern<V>), dim3((uint32_t)nparts),
+                     dim3(256), 0, (hipStream_t)stream, A, n, F, rpb, Gpart);
+  hipLaunchKernelGGL((gram_det_fold_kern<V>), dim3(1), dim3(256), 0,
+                     (hipStream_t)stream, Gpart, nparts, F, G);
+  return launch_rc();
+}
+
+int colacc(const double * A, int64_t n, int F, int which, double * out,
+           void * stream) {
   hipLaunchKernelGGL(colacc_kern, dim3(256), dim3(256), 0,
                      (hipStream_t)stream, A, n, F, which, out);
+  return launch_rc();
 }
-extern "C" void splatt_hip_colscale_f64(double * A, int64_t n, int F,
-                                        const double * lam, void * stream) {
+
+int colscale(double * A, int64_t n, int F, const double * lam,
+             void * stream) {
   hipLaunchKernelGGL(colscale_kern, dim3(512), dim3(256), 0,
                      (hipStream_t)stream, A, n, F, lam);
+  return launch_rc();
 }
-extern "C" void splatt_hip_coldot_f64(const double * X, const double * A,
-                                      int64_t n, int F, double * out,
-                                      void * stream) {
+
+int coldot(const double * X, const double * A, int64_t n, int F,
+           double * out, void * stream) {
   hipLaunchKernelGGL(coldot_kern, dim3(256), dim3(256), 0,
                      (hipStream_t)stream, X, A, n, F, out);
+  return launch_rc();
 }
 
-extern "C" int splatt_hip_rowsolve_f64(const double * A, const double * B,
-                                       double * C, int64_t n, int F,
-                                       void * stream) {
-  return launch_rowsolve<double>(A, B, C, n, F, (hipStream_t)stream);
-}
-extern "C" int splatt_hip_rowsolve_f32(const float * A, const float * B,
-                                       float * C, int64_t n, int F,
-                                       void * stream) {
-  return launch_rowsolve<float>(A, B, C, n, F, (hipStream_t)stream);
+template <typename V>
+int rowsolve(const V * A, const V * B, V * C, int64_t n, int F,
+             void * stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int rows_pb = 256 / (F < 256 ? F : 256);
+  int64_t blocks = (n + rows_pb - 1) / rows_pb;
+  if (blocks > 8192) blocks = 8192;          // grid-stride beyond this
+  if (blocks < 1) blocks = 1;
+  dim3 g((uint32_t)blocks), b(256);
+  switch (F) {
+    case 4:  hipLaunchKernelGGL((rowsolve_kern<V, 4>),  g, b, 0, st, A, B, C, n); break;
+    case 8:  hipLaunchKernelGGL((rowsolve_kern<V, 8>),  g, b, 0, st, A, B, C, n); break;
+    case 16: hipLaunchKernelGGL((rowsolve_kern<V, 16>), g, b, 0, st, A, B, C, n); break;
+    case 32: hipLaunchKernelGGL((rowsolve_kern<V, 32>), g, b, 0, st, A, B, C, n); break;
+    case 64: hipLaunchKernelGGL((rowsolve_kern<V, 64>), g, b, 0, st, A, B, C, n); break;
+    default: return -1;
+  }
+  return launch_rc();
 }
 
-extern "C" void splatt_hip_gram_f64(const double * A, int64_t n, int F,
-                                    double * G, void * stream) {
-  launch_gram<double>(A, n, F, G, (hipStream_t)stream);
+template <typename V>
+int gram(const V * A, int64_t n, int F, V * G, void * stream) {
+  launch_gram<V>(A, n, F, G, (hipStream_t)stream);
+  return launch_rc();
 }
-extern "C" void splatt_hip_gram_f32(const float * A, int64_t n, int F,
-                                    float * G, void * stream) {
-  launch_gram<float>(A, n, F, G, (hipStream_t)stream);
-}
-extern "C" void splatt_hip_spd_inverse_f64(const double * G, double * Ginv,
-                                           int F, void * stream) {
-  HadTab<double> tab{};
+
+template <typename V>
+int spd_inverse(const V * G, V * Ginv, int F, void * stream) {
+  HadTab<V> tab{};
   tab.g[0] = G;
   tab.n = 1;
-  hipLaunchKernelGGL((spd_inverse_kern<double>), dim3(1), dim3(64), 0,
-                     (hipStream_t)stream, tab, 0.0, Ginv, F,
-                     (double *)nullptr, (double *)nullptr, (double *)nullptr);
-}
-extern "C" void splatt_hip_spd_inverse_f32(const float * G, float * Ginv,
-                                           int F, void * stream) {
-  HadTab<float> tab{};
-  tab.g[0] = G;
-  tab.n = 1;
-  hipLaunchKernelGGL((spd_inverse_kern<float>), dim3(1), dim3(64), 0,
-                     (hipStream_t)stream, tab, 0.0f, Ginv, F,
-                     (float *)nullptr, (float *)nullptr, (float *)nullptr);
+  hipLaunchKernelGGL((spd_inverse_kern<V>), dim3(1), dim3(64), 0,
+                     (hipStream_t)stream, tab, (V)0, Ginv, F, (V *)nullptr,
+                     (V *)nullptr, (V *)nullptr);
+  return launch_rc();
 }
 
-// Front of the fused ALS tail (als_tail.hip), one launch: Ginv = inverse of
-// (grams[0] .* ... .* grams[ngrams-1] + reg*I), and the tail's accumulators
-// reset (any of the three may be null). ngrams == 0 only resets. Returns
-// the launch status (0 = ok), -1 for F > 64 or more than 8 matrices.
-extern "C" int splatt_hip_als_prep_f64(const double * const * grams,
-                                       int ngrams, double reg, double * Ginv,
-                                       int F, double * zero_gram,
-                                       double * lam_init, double * zero_inner,
-                                       void * stream) {
+template int gram_det<double>(const double *, int64_t, int, double *,
+                              int64_t, double *, void *);
+template int gram_det<float>(const float *, int64_t, int, float *, int64_t,
+                             float *, void *);
+template int rowsolve<double>(const double *, const double *, double *,
+                              int64_t, int, void *);
+template int rowsolve<float>(const float *, const float *, float *, int64_t,
+                             int, void *);
+template int gram<double>(const double *, int64_t, int, double *, void *);
+template int gram<float>(const float *, int64_t, int, float *, void *);
+template int spd_inverse<double>(const double *, double *, int, void *);
+template int spd_inverse<float>(const float *, float *, int, void *);
+
+int als_prep(const double * const * grams, int ngrams, double reg,
+             double * Ginv, int F, double * zero_gram, double * lam_init,
+             double * zero_inner, void * stream) {
   if (F < 1 || F > 64 || ngrams < 0 || ngrams > 8) return -1;
   HadTab<double> tab{};
   for (int o = 0; o < ngrams; ++o) tab.g[o] = grams[o];
@@ -502,5 +481,8 @@ extern "C" int splatt_hip_als_prep_f64(const double * const * grams,
   hipLaunchKernelGGL((spd_inverse_kern<double>), dim3(1), dim3(64), 0,
                      (hipStream_t)stream, tab, reg, Ginv, F, zero_gram,
                      lam_init, zero_inner);
-  return (int)hipGetLastError();
+  return launch_rc();
 }
+
+}  // namespace hip
+}  // namespace splatt

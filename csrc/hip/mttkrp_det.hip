@@ -30,20 +30,11 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "store_types.hpp"
 
 namespace {
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ int64_t min64(int64_t a, int64_t b) {
-  return a < b ? a : b;
-}
-
-template <typename T>
-__device__ __forceinline__ T ldnt(const T * p) {
-  return __builtin_nontemporal_load(p);
-}
 
 // walker -> its contiguous nnz range (the flat-v2 span decomposition:
 // wave `wid` covers [wid*span, ..), split into R = WAVE/F group spans)
@@ -198,7 +189,6 @@ mttkrp_det_fixup_kern(const int32_t * __restrict__ key, int64_t nnz,
 // of workspace (Python gates on SPLATT_DET_MB, falling back to the
 // key-sorted kernel above).
 constexpr int WPB6 = 4;
-inline bool det_spec_ok(int F);
 
 template <typename V, int F, int NOTHER, typename S = V>
 __global__ void __launch_bounds__(WPB6 * WAVE)
@@ -391,29 +381,33 @@ det6_fold_kern(const V * __restrict__ outb, int64_t nbuckets,
   }
 }
 
+}  // namespace
+
+namespace splatt {
+namespace hip {
+
 template <typename V>
-int launch_det6(const int32_t * pack, const V * const mats[3],
-                const V * vals, const int64_t * blk_start,
-                const int64_t * blk_end, const int32_t * blk_row0,
-                const int64_t * blk_bucket_p0,
+int mttkrp_det6(const int32_t * pack, const V * const * mats, const V * vals,
+                const int64_t * blk_start, const int64_t * blk_end,
+                const int32_t * blk_row0, const int64_t * blk_bucket_p0,
                 int64_t nblocks, int32_t chunk, int32_t dim0,
                 int64_t nrows_out, int64_t nbuckets, V * outb, V * side,
-                V * out, int rank, int nother, hipStream_t st) {
-  if (!det_spec_ok(rank) || nother > 3) return -1;
+                V * out, int rank, int nother, void * stream) {
+  if (!spec_ok(rank) || nother > 3) return -1;
+  hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(outb, 0,
                        (size_t)nbuckets * nrows_out * rank * sizeof(V), st);
-  constexpr int WAVE_ = 64;
   // single-key walkers never write their slot-1 side entry: zero both
-  const int64_t nwalk = nblocks * 4 * (WAVE_ / rank);
+  const int64_t nwalk = nblocks * 4 * (WAVE / rank);
   (void)hipMemsetAsync(side, 0, (size_t)nwalk * 2 * rank * sizeof(V), st);
-  dim3 grid((uint32_t)nblocks), block(WPB6 * WAVE_);
+  dim3 grid((uint32_t)nblocks), block(WPB6 * WAVE);
   const size_t lds = (size_t)chunk * rank * sizeof(V);
 #define D6(F_, N_) \
   { hipLaunchKernelGGL((mttkrp_det6_kern<V, F_, N_>), grid, block, lds, st, \
         pack, mats[0], mats[1], mats[2], vals, blk_start, blk_end, \
         blk_row0, chunk, dim0, nrows_out, outb, side); \
     const int tpb = 256; \
-    const int64_t nw = nblocks * (4 * (WAVE_ / F_)); \
+    const int64_t nw = nblocks * (4 * (WAVE / F_)); \
     const int64_t fb = (nw + tpb / F_ - 1) / (tpb / F_); \
     hipLaunchKernelGGL((mttkrp_det6_fixup_kern<V, F_>), \
         dim3((uint32_t)fb), dim3(tpb), 0, st, pack, blk_start, blk_end, \
@@ -428,35 +422,25 @@ int launch_det6(const int32_t * pack, const V * const mats[3],
   const int64_t elems = nrows_out * rank;
   hipLaunchKernelGGL((det6_fold_kern<V>), dim3(512), dim3(256), 0, st,
                      outb, nbuckets, elems, out);
-  return 0;
+  return launch_rc();
 }
 
-inline int64_t det_pick_span(int64_t nnz) {
-  const char * e = getenv("SPLATT_SPAN_WAVES");
-  const int64_t target_waves = e ? atoll(e) : 65536;
-  int64_t span = nnz / target_waves;
-  if (span < 256) span = 256;
-  if (span > 16384) span = 16384;
-  return span;
-}
-
-inline int64_t det_nwalkers(int64_t nnz, int rank) {
-  const int64_t span = det_pick_span(nnz);
+// two side slots of `rank` elements per walker (WAVE / rank per wave)
+int64_t flat_det_ws(int64_t nnz, int rank) {
+  if (!spec_ok(rank)) return -1;
+  const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
-  return nwaves * (WAVE / rank);
-}
-
-inline bool det_spec_ok(int F) {
-  return F == 4 || F == 8 || F == 16 || F == 32 || F == 64;
+  return nwaves * (WAVE / rank) * 2 * rank;
 }
 
 template <typename V>
-int launch_flat_det(const int32_t * key, const int32_t * const idx[8],
-                    const V * const mats[8], const V * vals, int64_t nnz,
+int mttkrp_flat_det(const int32_t * key, const int32_t * const * idx,
+                    const V * const * mats, const V * vals, int64_t nnz,
                     V * out, V * side, int64_t side_elems, int rank,
-                    int nother, hipStream_t st) {
-  if (!det_spec_ok(rank) || nother > 4) return -1;
-  const int64_t span = det_pick_span(nnz);
+                    int nother, void * stream) {
+  if (!spec_ok(rank) || nother > 4) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
   const int64_t nw = nwaves * (WAVE / rank);
   if (side_elems < nw * 2 * rank) return -2;
@@ -489,62 +473,24 @@ int launch_flat_det(const int32_t * key, const int32_t * const idx[8],
 #undef DK
 #undef DFIX
 #undef DARGS
-  return 0;
+  return launch_rc();
 }
 
-}  // namespace
+#define DET6(V)                                                            \
+  template int mttkrp_det6<V>(                                             \
+      const int32_t *, const V * const *, const V *, const int64_t *,      \
+      const int64_t *, const int32_t *, const int64_t *, int64_t, int32_t, \
+      int32_t, int64_t, int64_t, V *, V *, V *, int, int, void *);
+#define FLAT_DET(V)                                                        \
+  template int mttkrp_flat_det<V>(                                         \
+      const int32_t *, const int32_t * const *, const V * const *,         \
+      const V *, int64_t, V *, V *, int64_t, int, int, void *);
+DET6(double)
+DET6(float)
+FLAT_DET(double)
+FLAT_DET(float)
+#undef FLAT_DET
+#undef DET6
 
-extern "C" int splatt_hip_mttkrp_det6_f64(
-    const int32_t * pack, const double * m0, const double * m1,
-    const double * m2, const double * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0,
-    const int64_t * blk_bucket_p0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, int64_t nrows_out, int64_t nbuckets,
-    double * outb, double * side, double * out, int rank, int nother,
-    void * stream) {
-  const double * mats[3] = {m0, m1, m2};
-  return launch_det6<double>(pack, mats, vals, blk_start, blk_end,
-                             blk_row0, blk_bucket_p0, nblocks, chunk, dim0, nrows_out,
-                             nbuckets, outb, side, out, rank, nother,
-                             (hipStream_t)stream);
-}
-
-extern "C" int splatt_hip_mttkrp_det6_f32(
-    const int32_t * pack, const float * m0, const float * m1,
-    const float * m2, const float * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0,
-    const int64_t * blk_bucket_p0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, int64_t nrows_out, int64_t nbuckets,
-    float * outb, float * side, float * out, int rank, int nother,
-    void * stream) {
-  const float * mats[3] = {m0, m1, m2};
-  return launch_det6<float>(pack, mats, vals, blk_start, blk_end,
-                            blk_row0, blk_bucket_p0, nblocks, chunk, dim0,
-                            nrows_out, nbuckets, outb, side, out, rank,
-                            nother, (hipStream_t)stream);
-}
-
-extern "C" int64_t splatt_hip_flat_det_ws(int64_t nnz, int rank) {
-  if (!det_spec_ok(rank)) return -1;
-  return det_nwalkers(nnz, rank) * 2 * rank;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_det_f64(
-    const int32_t * key, const int32_t * const * idx,
-    const double * const * mats, const double * vals, int64_t nnz,
-    double * out, double * side, int64_t side_elems, int rank, int nother,
-    void * stream) {
-  return launch_flat_det<double>(key, idx, mats, vals, nnz, out, side,
-                                 side_elems, rank, nother,
-                                 (hipStream_t)stream);
-}
-
-extern "C" int splatt_hip_mttkrp_flat_det_f32(
-    const int32_t * key, const int32_t * const * idx,
-    const float * const * mats, const float * vals, int64_t nnz,
-    float * out, float * side, int64_t side_elems, int rank, int nother,
-    void * stream) {
-  return launch_flat_det<float>(key, idx, mats, vals, nnz, out, side,
-                                side_elems, rank, nother,
-                                (hipStream_t)stream);
-}
+}  // namespace hip
+}  // namespace splatt

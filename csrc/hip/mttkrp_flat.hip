@@ -23,27 +23,15 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include <type_traits>
+
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "store_types.hpp"
 
 namespace {
 using splatt_store::bf16;
 using splatt_store::to_compute;
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-template <typename V>
-__device__ __forceinline__ void atomic_add_g(V * p, V v) {
-  unsafeAtomicAdd(p, v);
-}
-
-// streamed-once arrays (key/idx/vals) are loaded non-temporally so they do
-// not evict the factor-row working set from the per-XCD L2s
-template <typename T>
-__device__ __forceinline__ T ldnt(const T * p) {
-  return __builtin_nontemporal_load(p);
-}
 
 // ---------------------------------------------------------- spec kernels
 // F lanes per column group, R = 64/F groups each walking a contiguous
@@ -414,19 +402,6 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
   atomic_add_g(&out[(int64_t)cur * F + c], acc);
 }
 
-inline int64_t pick_span(int64_t nnz) {
-  const char * e = getenv("SPLATT_SPAN_WAVES");   // tuning knob
-  const int64_t target_waves = e ? atoll(e) : 65536;
-  int64_t span = nnz / target_waves;
-  if (span < 256) span = 256;
-  if (span > 16384) span = 16384;
-  return span;
-}
-
-inline bool spec_ok(int F) {
-  return F == 4 || F == 8 || F == 16 || F == 32 || F == 64;
-}
-
 inline int pick_unroll() {
   // A/B lever: 0 (default) = full-line staged v7 kernel (v2 at rank 4 or
   // when the streams are not co-aligned); 1 = force v2; 2 = v2 with gather
@@ -507,14 +482,11 @@ bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
 }
 
 // storage-typed launcher (reduced-precision factor STORE for non-staged
-// HBM-bound dispatches): v7, else v2
+// HBM-bound dispatches) for what v7 declines: v2
 template <typename V, typename S>
 void launch_flat_store(const int32_t * key, const int32_t * const idx[8],
                        const S * const mats[8], const V * vals, int64_t nnz,
                        V * out, int rank, int nother, hipStream_t st) {
-  if (launch_flat7<V, S>(key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank,
-                         nother, st))
-    return;
   const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
   const int wpb = 4;
@@ -788,13 +760,12 @@ mttkrp_flat_generic_kern(const int32_t * __restrict__ key,
   }
 }
 
+// what v7 declines on a key stream: v2 (or the SPLATT_MTTKRP_U lever's
+// kernel) at spec ranks and <= 5 modes, the generic kernel otherwise
 template <typename V>
 void launch_flat(const int32_t * key, const int32_t * const idx[8],
                  const V * const mats[8], const V * vals, int64_t nnz,
                  V * out, int rank, int nother, hipStream_t st) {
-  if (launch_flat7<V, V>(key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank,
-                         nother, st))
-    return;
   const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
   const int wpb = 4;
@@ -851,114 +822,75 @@ void launch_flat(const int32_t * key, const int32_t * const idx[8],
 #undef GARGS
 }
 
+#define FLAT7_SIG(V, S, VS)                                                \
+  const int32_t *, const int64_t *, int64_t, int64_t,                      \
+  const int32_t * const *, const S * const *, const VS *, int64_t, V *,    \
+  int, int
+#define FLAT_SIG(V)                                                        \
+  const int32_t *, const int32_t * const *, const V * const *, const V *,  \
+  int64_t, V *, int, int
+// Kernels land in the code object in the order they are first instantiated.
+// These keep it what it has been (the key-stream kernels of both types, then
+// the v7 instances of every type combination, then the v2 instances of the
+// reduced-precision stores), so that a change of the launcher layer leaves
+// the device code bit-identical.
+template void launch_flat<double>(FLAT_SIG(double), hipStream_t);
+template void launch_flat<float>(FLAT_SIG(float), hipStream_t);
+template bool launch_flat7<double, double, double>(
+    FLAT7_SIG(double, double, double), hipStream_t);
+template bool launch_flat7<float, float, float>(
+    FLAT7_SIG(float, float, float), hipStream_t);
+template bool launch_flat7<double, float, double>(
+    FLAT7_SIG(double, float, double), hipStream_t);
+template bool launch_flat7<double, bf16, double>(
+    FLAT7_SIG(double, bf16, double), hipStream_t);
+template bool launch_flat7<double, double, float>(
+    FLAT7_SIG(double, double, float), hipStream_t);
+#undef FLAT_SIG
+
 }  // namespace
 
-extern "C" void splatt_hip_mttkrp_flat_f64(
-    const int32_t * key, const int32_t * const * idx,
-    const double * const * mats,
-    const double * vals, int64_t nnz, double * out, int rank, int nother,
-    void * stream) {
-  launch_flat<double>(key, idx, mats, vals, nnz, out, rank, nother,
-                      (hipStream_t)stream);
+namespace splatt {
+namespace hip {
+
+template <typename V, typename S, typename VS>
+int mttkrp_flat(const int32_t * key, const int64_t * rowptr, int64_t nrows,
+                int64_t p0, const int32_t * const * idx,
+                const S * const * mats, const VS * vals, int64_t nnz, V * out,
+                int rank, int nother, void * stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (rowptr ? launch_flat7<V, S, VS>(nullptr, rowptr, nrows, p0, idx, mats,
+                                      vals, nnz, out, rank, nother, st)
+             : launch_flat7<V, S, VS>(key, nullptr, 0, 0, idx, mats, vals,
+                                      nnz, out, rank, nother, st))
+    return launch_rc();
+  // v7 declined. A key stream of V values has the older kernels behind it.
+  if constexpr (std::is_same<VS, V>::value) {
+    if (rowptr) return -1;
+    if constexpr (std::is_same<S, V>::value) {
+      launch_flat<V>(key, idx, mats, vals, nnz, out, rank, nother, st);
+      return launch_rc();
+    } else if (spec_ok(rank) && nother <= 4) {
+      launch_flat_store<V, S>(key, idx, mats, vals, nnz, out, rank, nother,
+                              st);
+      return launch_rc();
+    }
+  }
+  return -1;
 }
 
-extern "C" void splatt_hip_mttkrp_flat_f32(
-    const int32_t * key, const int32_t * const * idx,
-    const float * const * mats,
-    const float * vals, int64_t nnz, float * out, int rank, int nother,
-    void * stream) {
-  launch_flat<float>(key, idx, mats, vals, nnz, out, rank, nother,
-                     (hipStream_t)stream);
-}
+// every type combination the flat family exists in
+template int mttkrp_flat<double, double, double>(
+    FLAT7_SIG(double, double, double), void *);
+template int mttkrp_flat<float, float, float>(
+    FLAT7_SIG(float, float, float), void *);
+template int mttkrp_flat<double, float, double>(
+    FLAT7_SIG(double, float, double), void *);
+template int mttkrp_flat<double, bf16, double>(
+    FLAT7_SIG(double, bf16, double), void *);
+template int mttkrp_flat<double, double, float>(
+    FLAT7_SIG(double, double, float), void *);
+#undef FLAT7_SIG
 
-// Row-pointer entry points (root output of a key-sorted stream): `rowptr`
-// (int64, nrows + 1 entries, GLOBAL stream positions) stands in for the key
-// stream; `p0` is the global stream position of the launch's first nonzero,
-// i.e. idx/vals point at element p0. Return 0 when launched, -1 when the
-// launch does not qualify for the v7 kernel (see launch_flat7) — the
-// caller then uses the key-stream entry points above.
-extern "C" int splatt_hip_mttkrp_flat_rp_f64(
-    const int64_t * rowptr, int64_t nrows, int64_t p0,
-    const int32_t * const * idx, const double * const * mats,
-    const double * vals, int64_t nnz, double * out, int rank, int nother,
-    void * stream) {
-  return launch_flat7<double, double>(nullptr, rowptr, nrows, p0, idx, mats,
-                                      vals, nnz, out, rank, nother,
-                                      (hipStream_t)stream) ? 0 : -1;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_rp_f32(
-    const int64_t * rowptr, int64_t nrows, int64_t p0,
-    const int32_t * const * idx, const float * const * mats,
-    const float * vals, int64_t nnz, float * out, int rank, int nother,
-    void * stream) {
-  return launch_flat7<float, float>(nullptr, rowptr, nrows, p0, idx, mats,
-                                    vals, nnz, out, rank, nother,
-                                    (hipStream_t)stream) ? 0 : -1;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_rp_f64f32(
-    const int64_t * rowptr, int64_t nrows, int64_t p0,
-    const int32_t * const * idx, const float * const * mats,
-    const double * vals, int64_t nnz, double * out, int rank, int nother,
-    void * stream) {
-  return launch_flat7<double, float>(nullptr, rowptr, nrows, p0, idx, mats,
-                                     vals, nnz, out, rank, nother,
-                                     (hipStream_t)stream) ? 0 : -1;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_rp_f64bf16(
-    const int64_t * rowptr, int64_t nrows, int64_t p0,
-    const int32_t * const * idx, const uint16_t * const * mats,
-    const double * vals, int64_t nnz, double * out, int rank, int nother,
-    void * stream) {
-  return launch_flat7<double, bf16>(nullptr, rowptr, nrows, p0, idx,
-                                    (const bf16 * const *)mats, vals, nnz,
-                                    out, rank, nother,
-                                    (hipStream_t)stream) ? 0 : -1;
-}
-
-// f32 value STREAM (f64 factors and accumulation) on the v7 kernel, row
-// pointers or key; `vals` is the 4-byte copy of f32-exact values. -1 =
-// declined (nothing launched): the caller runs the 8-byte stream.
-extern "C" int splatt_hip_mttkrp_flat_rp_f64v32(
-    const int64_t * rowptr, int64_t nrows, int64_t p0,
-    const int32_t * const * idx, const double * const * mats,
-    const float * vals, int64_t nnz, double * out, int rank, int nother,
-    void * stream) {
-  return launch_flat7<double, double, float>(
-             nullptr, rowptr, nrows, p0, idx, mats, vals, nnz, out, rank,
-             nother, (hipStream_t)stream) ? 0 : -1;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_f64v32(
-    const int32_t * key, const int32_t * const * idx,
-    const double * const * mats, const float * vals, int64_t nnz,
-    double * out, int rank, int nother, void * stream) {
-  return launch_flat7<double, double, float>(
-             key, nullptr, 0, 0, idx, mats, vals, nnz, out, rank, nother,
-             (hipStream_t)stream) ? 0 : -1;
-}
-
-// reduced-precision factor STORAGE (f64 accumulate) on the v7/v2 path;
-// returns nonzero for unsupported (non-spec) ranks
-extern "C" int splatt_hip_mttkrp_flat_f64f32(
-    const int32_t * key, const int32_t * const * idx,
-    const float * const * mats, const double * vals, int64_t nnz,
-    double * out, int rank, int nother, void * stream) {
-  if (!spec_ok(rank) || nother > 4) return -1;
-  launch_flat_store<double, float>(key, idx, mats, vals, nnz, out, rank,
-                                   nother, (hipStream_t)stream);
-  return 0;
-}
-
-extern "C" int splatt_hip_mttkrp_flat_f64bf16(
-    const int32_t * key, const int32_t * const * idx,
-    const uint16_t * const * mats, const double * vals, int64_t nnz,
-    double * out, int rank, int nother, void * stream) {
-  if (!spec_ok(rank) || nother > 4) return -1;
-  launch_flat_store<double, bf16>(key, idx,
-                                  (const bf16 * const *)mats, vals, nnz,
-                                  out, rank, nother, (hipStream_t)stream);
-  return 0;
-}
+}  // namespace hip
+}  // namespace splatt

@@ -17,18 +17,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "device_common.hpp"
+#include "launchers.hpp"
+
 namespace {
-
-constexpr int WAVE = 64;
-
-__device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-template <typename V>
-__device__ __forceinline__ void atomic_add_g(V * p, V v) {
-  // CDNA has native global fadd for f32/f64; unsafeAtomicAdd emits it
-  // (plain atomicAdd lowers to a CAS loop without -munsafe-fp-atomics).
-  unsafeAtomicAdd(p, v);
-}
 
 // first index i in [0,n) with a[i] > key
 __device__ __forceinline__ int64_t upper_bound_i64(
@@ -254,7 +246,10 @@ mttkrp3_generic_kern(const int64_t * __restrict__ fptr0,
 
 // --------------------------------------------------------------- launchers
 
-inline int64_t pick_span(int64_t nnz) {
+// Not device_common.hpp's pick_span: the CSF walk keeps a fixed 65536-wave
+// target and does not read SPLATT_SPAN_WAVES (that knob tunes the flat
+// kernels only; this family is the comparison algorithm).
+inline int64_t csf_pick_span(int64_t nnz) {
   // enough waves to fill 256 CUs x 8 XCDs many times over, but >=256 nnz
   // of work per wave so the binary searches amortize
   int64_t span = nnz / 65536;
@@ -268,7 +263,7 @@ inline int64_t pick_span(int64_t nnz) {
 // class templates).
 #define LAUNCH_SPEC(KERN, V, F_RT)                                            \
   do {                                                                        \
-    const int64_t span_ = pick_span(nnz);                                     \
+    const int64_t span_ = csf_pick_span(nnz);                                 \
     const int64_t nwaves_ = (nnz + span_ - 1) / span_;                        \
     const int wpb_ = 4; /* 256-thread blocks */                               \
     const int64_t nblocks_ = (nwaves_ + wpb_ - 1) / wpb_;                     \
@@ -301,32 +296,67 @@ void launch_generic(int which, int rank, const int64_t * fptr0,
     hipLaunchKernelGGL((mttkrp3_generic_kern<V, 2>), grid, block, 0, st, fptr0, fids0, fptr1, fids1, fids2, vals, nslices, nfibs, nnz, rank, Ma, Mb, out);
 }
 
-inline bool spec_ok(int F) {
-  return F == 4 || F == 8 || F == 16 || F == 32 || F == 64;
+// one member of the family: the spec kernel at a spec rank, else generic
+template <typename V, int WHICH>
+void launch_csf3(const int64_t * fptr0, const int32_t * fids0,
+                 const int64_t * fptr1, const int32_t * fids1,
+                 const int32_t * fids2, const V * vals, int64_t nslices,
+                 int64_t nfibs, int64_t nnz, const V * Ma, const V * Mb,
+                 V * out, int rank, hipStream_t st) {
+  if (spec_ok(rank)) {
+    if constexpr (WHICH == 0) LAUNCH_SPEC(mttkrp_root3_kern, V, rank);
+    else if constexpr (WHICH == 1) LAUNCH_SPEC(mttkrp_intl3_kern, V, rank);
+    else LAUNCH_SPEC(mttkrp_leaf3_kern, V, rank);
+  } else {
+    launch_generic<V>(WHICH, rank, fptr0, fids0, fptr1, fids1, fids2, vals,
+                      nslices, nfibs, nnz, Ma, Mb, out, st);
+  }
 }
+
+#define CSF3_SIG(V)                                                          \
+  const int64_t *, const int32_t *, const int64_t *, const int32_t *,        \
+  const int32_t *, const V *, int64_t, int64_t, int64_t, const V *,          \
+  const V *, V *, int
+// Kernels land in the code object in the order they are first instantiated.
+// These keep it what it has been (root f64/f32, internal, leaf), so that a
+// change of the launcher layer leaves the device code bit-identical.
+template void launch_csf3<double, 0>(CSF3_SIG(double), hipStream_t);
+template void launch_csf3<float, 0>(CSF3_SIG(float), hipStream_t);
+template void launch_csf3<double, 1>(CSF3_SIG(double), hipStream_t);
+template void launch_csf3<float, 1>(CSF3_SIG(float), hipStream_t);
+template void launch_csf3<double, 2>(CSF3_SIG(double), hipStream_t);
+template void launch_csf3<float, 2>(CSF3_SIG(float), hipStream_t);
 
 }  // namespace
 
-#define DEFINE_ENTRY(NAME, VTYPE, KERN, WHICH)                               \
-  extern "C" void NAME(const int64_t * fptr0, const int32_t * fids0,         \
-                       const int64_t * fptr1, const int32_t * fids1,         \
-                       const int32_t * fids2, const VTYPE * vals,            \
-                       int64_t nslices, int64_t nfibs, int64_t nnz,          \
-                       const VTYPE * Ma, const VTYPE * Mb, VTYPE * out,      \
-                       int rank, void * stream) {                            \
-    hipStream_t st = (hipStream_t)stream;                                    \
-    if (spec_ok(rank))                                                       \
-      LAUNCH_SPEC(KERN, VTYPE, rank);                                        \
-    else                                                                     \
-      launch_generic<VTYPE>(WHICH, rank, fptr0, fids0, fptr1, fids1, fids2,  \
-                            vals, nslices, nfibs, nnz, Ma, Mb, out, st);     \
-  }
+namespace splatt {
+namespace hip {
 
-DEFINE_ENTRY(splatt_hip_mttkrp_root3_f64, double, mttkrp_root3_kern, 0)
-DEFINE_ENTRY(splatt_hip_mttkrp_root3_f32, float,  mttkrp_root3_kern, 0)
-DEFINE_ENTRY(splatt_hip_mttkrp_intl3_f64, double, mttkrp_intl3_kern, 1)
-DEFINE_ENTRY(splatt_hip_mttkrp_intl3_f32, float,  mttkrp_intl3_kern, 1)
-DEFINE_ENTRY(splatt_hip_mttkrp_leaf3_f64, double, mttkrp_leaf3_kern, 2)
-DEFINE_ENTRY(splatt_hip_mttkrp_leaf3_f32, float,  mttkrp_leaf3_kern, 2)
+template <typename V>
+int mttkrp_csf3(int which, const int64_t * fptr0, const int32_t * fids0,
+                const int64_t * fptr1, const int32_t * fids1,
+                const int32_t * fids2, const V * vals, int64_t nslices,
+                int64_t nfibs, int64_t nnz, const V * Ma, const V * Mb,
+                V * out, int rank, void * stream) {
+  hipStream_t st = (hipStream_t)stream;
+#define CSF3_ARGS fptr0, fids0, fptr1, fids1, fids2, vals, nslices, nfibs, \
+                  nnz, Ma, Mb, out, rank, st
+  if (which == 0) launch_csf3<V, 0>(CSF3_ARGS);
+  else if (which == 1) launch_csf3<V, 1>(CSF3_ARGS);
+  else launch_csf3<V, 2>(CSF3_ARGS);
+#undef CSF3_ARGS
+  return launch_rc();
+}
 
-extern "C" int splatt_hip_kernels_arch(void) { return 950; }
+template int mttkrp_csf3<double>(int, CSF3_SIG(double), void *);
+template int mttkrp_csf3<float>(int, CSF3_SIG(float), void *);
+#undef CSF3_SIG
+
+int kernels_arch() { return 950; }
+
+const char * error_string(int rc) {
+  return hipGetErrorString((hipError_t)rc);
+}
+
+}  // namespace hip
+}  // namespace splatt

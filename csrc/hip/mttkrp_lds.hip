@@ -19,6 +19,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "store_types.hpp"
 
 namespace {
@@ -26,20 +28,7 @@ using splatt_store::bf16;
 using splatt_store::VecElemT;
 using splatt_store::to_compute;
 
-constexpr int WAVE = 64;
 constexpr int WPB = 4;   // waves per block
-
-__device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
-template <typename V>
-__device__ __forceinline__ void atomic_add_g(V * p, V v) {
-  unsafeAtomicAdd(p, v);
-}
-
-template <typename T>
-__device__ __forceinline__ T ldnt(const T * p) {
-  return __builtin_nontemporal_load(p);
-}
 
 // i0/m0 = the STAGED (bucketed) level; i1.. = the remaining levels.
 template <typename V, int F, int NOTHER>
@@ -264,12 +253,18 @@ mttkrp_flat6_kern(const int * __restrict__ pack_raw,
   atomic_add_g(&out[(int64_t)cur * F + c], acc);
 }
 
-template <typename V, typename S = V>
-void launch_flat6(const int32_t * pack, const S * const mats[3],
-                  const V * vals, const int64_t * blk_start,
-                  const int64_t * blk_end, const int32_t * blk_row0,
-                  int64_t nblocks, int32_t chunk, int32_t dim0, V * out,
-                  int rank, int nother, hipStream_t st) {
+}  // namespace
+
+namespace splatt {
+namespace hip {
+
+template <typename V, typename S>
+int mttkrp_flat6(const int32_t * pack, const S * const * mats,
+                 const V * vals, const int64_t * blk_start,
+                 const int64_t * blk_end, const int32_t * blk_row0,
+                 int64_t nblocks, int32_t chunk, int32_t dim0, V * out,
+                 int rank, int nother, void * stream) {
+  hipStream_t st = (hipStream_t)stream;
   const char * we = getenv("SPLATT_V6_WPB");
   const int wpb6 = (we && atoi(we) == 8) ? 8 : WPB;
   dim3 grid((uint32_t)nblocks), block(wpb6 * WAVE);
@@ -296,15 +291,16 @@ void launch_flat6(const int32_t * pack, const S * const mats[3],
 #undef L6F
 #undef L6
 #undef ARGS6
+  return launch_rc();
 }
 
 template <typename V>
-void launch_flat5(const int32_t * key, const int32_t * const idx[4],
-                  const V * const mats[4], const V * vals,
-                  const int64_t * blk_start, const int64_t * blk_end,
-                  const int32_t * blk_row0, int64_t nblocks, int32_t chunk,
-                  int32_t dim0, V * out, int rank, int nother,
-                  hipStream_t st) {
+int mttkrp_flat5(const int32_t * key, const int32_t * const * idx,
+                 const V * const * mats, const V * vals,
+                 const int64_t * blk_start, const int64_t * blk_end,
+                 const int32_t * blk_row0, int64_t nblocks, int32_t chunk,
+                 int32_t dim0, V * out, int rank, int nother, void * stream) {
+  hipStream_t st = (hipStream_t)stream;
   dim3 grid((uint32_t)nblocks), block(WPB * WAVE);
   const size_t lds = (size_t)chunk * rank * sizeof(V);
 #define ARGS key, idx[0], idx[1], idx[2], idx[3], mats[0], mats[1], mats[2], \
@@ -323,84 +319,28 @@ void launch_flat5(const int32_t * key, const int32_t * const idx[4],
 #undef L5F
 #undef L5
 #undef ARGS
+  return launch_rc();
 }
 
-}  // namespace
+#define BLK_SIG const int64_t *, const int64_t *, const int32_t *, int64_t, \
+                int32_t, int32_t
+#define FLAT6(V, S)                                                        \
+  template int mttkrp_flat6<V, S>(const int32_t *, const S * const *,      \
+                                  const V *, BLK_SIG, V *, int, int, void *);
+#define FLAT5(V)                                                           \
+  template int mttkrp_flat5<V>(const int32_t *, const int32_t * const *,   \
+                               const V * const *, const V *, BLK_SIG, V *, \
+                               int, int, void *);
+FLAT6(double, double)
+FLAT6(float, float)
+// reduced-precision factor STORAGE (f64 accumulation)
+FLAT6(double, float)
+FLAT6(double, bf16)
+FLAT5(double)
+FLAT5(float)
+#undef FLAT5
+#undef FLAT6
+#undef BLK_SIG
 
-extern "C" void splatt_hip_mttkrp_flat6_f64(
-    const int32_t * pack, const double * m0, const double * m1,
-    const double * m2, const double * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, double * out, int rank, int nother,
-    void * stream) {
-  const double * mats[3] = {m0, m1, m2};
-  launch_flat6<double>(pack, mats, vals, blk_start, blk_end, blk_row0,
-                       nblocks, chunk, dim0, out, rank, nother,
-                       (hipStream_t)stream);
-}
-
-extern "C" void splatt_hip_mttkrp_flat6_f32(
-    const int32_t * pack, const float * m0, const float * m1,
-    const float * m2, const float * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, float * out, int rank, int nother,
-    void * stream) {
-  const float * mats[3] = {m0, m1, m2};
-  launch_flat6<float>(pack, mats, vals, blk_start, blk_end, blk_row0,
-                      nblocks, chunk, dim0, out, rank, nother,
-                      (hipStream_t)stream);
-}
-
-// reduced-precision factor STORAGE (f64 accumulation) — ROADMAP 2b
-extern "C" void splatt_hip_mttkrp_flat6_f64f32(
-    const int32_t * pack, const float * m0, const float * m1,
-    const float * m2, const double * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, double * out, int rank, int nother,
-    void * stream) {
-  const float * mats[3] = {m0, m1, m2};
-  launch_flat6<double, float>(pack, mats, vals, blk_start, blk_end,
-                              blk_row0, nblocks, chunk, dim0, out, rank,
-                              nother, (hipStream_t)stream);
-}
-
-extern "C" void splatt_hip_mttkrp_flat6_f64bf16(
-    const int32_t * pack, const uint16_t * m0, const uint16_t * m1,
-    const uint16_t * m2, const double * vals, const int64_t * blk_start,
-    const int64_t * blk_end, const int32_t * blk_row0, int64_t nblocks,
-    int32_t chunk, int32_t dim0, double * out, int rank, int nother,
-    void * stream) {
-  const bf16 * mats[3] = {(const bf16*)m0, (const bf16*)m1,
-                          (const bf16*)m2};
-  launch_flat6<double, bf16>(pack, mats, vals, blk_start, blk_end,
-                             blk_row0, nblocks, chunk, dim0, out, rank,
-                             nother, (hipStream_t)stream);
-}
-
-extern "C" void splatt_hip_mttkrp_flat5_f64(
-    const int32_t * key, const int32_t * i0, const int32_t * i1,
-    const int32_t * i2, const int32_t * i3, const double * m0,
-    const double * m1, const double * m2, const double * m3,
-    const double * vals, const int64_t * blk_start, const int64_t * blk_end,
-    const int32_t * blk_row0, int64_t nblocks, int32_t chunk, int32_t dim0,
-    double * out, int rank, int nother, void * stream) {
-  const int32_t * idx[4] = {i0, i1, i2, i3};
-  const double * mats[4] = {m0, m1, m2, m3};
-  launch_flat5<double>(key, idx, mats, vals, blk_start, blk_end, blk_row0,
-                       nblocks, chunk, dim0, out, rank, nother,
-                       (hipStream_t)stream);
-}
-
-extern "C" void splatt_hip_mttkrp_flat5_f32(
-    const int32_t * key, const int32_t * i0, const int32_t * i1,
-    const int32_t * i2, const int32_t * i3, const float * m0,
-    const float * m1, const float * m2, const float * m3,
-    const float * vals, const int64_t * blk_start, const int64_t * blk_end,
-    const int32_t * blk_row0, int64_t nblocks, int32_t chunk, int32_t dim0,
-    float * out, int rank, int nother, void * stream) {
-  const int32_t * idx[4] = {i0, i1, i2, i3};
-  const float * mats[4] = {m0, m1, m2, m3};
-  launch_flat5<float>(key, idx, mats, vals, blk_start, blk_end, blk_row0,
-                      nblocks, chunk, dim0, out, rank, nother,
-                      (hipStream_t)stream);
-}
+}  // namespace hip
+}  // namespace splatt

@@ -6,9 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-namespace splatt_store {
+#include "launchers.hpp"  // struct bf16
 
-struct bf16 { uint16_t v; };
+namespace splatt_store {
 
 template <typename S> struct VecElemT { using type = S; };
 template <> struct VecElemT<bf16> { using type = uint16_t; };

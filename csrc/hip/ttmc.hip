@@ -37,11 +37,12 @@
 // order. No atomics, fixed summation order: bitwise reproducible.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "device_common.hpp"
+#include "launchers.hpp"
 #include "mfma_acc.hpp"
 
 namespace {
 
-constexpr int WAVE = 64;
 constexpr int MAX_RANK = 32;
 constexpr int MAX_COLS = 4096;
 
@@ -211,7 +212,7 @@ int launch_tb(const TtmcTab & tab, const double * vals,
     default: hipLaunchKernelGGL((ttmc_mfma_kern<NO, TA, 4>), grid, block, 0, st, TARGS); break;
   }
 #undef TARGS
-  return (int)hipGetLastError();
+  return launch_rc();
 }
 
 template <int NO, typename... Args>
@@ -221,18 +222,17 @@ int launch_ta(int RA, Args... args) {
 
 }  // namespace
 
-extern "C" int splatt_hip_ttmc_max_cols() { return MAX_COLS; }
+namespace splatt {
+namespace hip {
 
-// segments [seg0, seg0+nseg) of one output mode. idx/mats/ranks: the
-// non-root levels 1..nother of the stream. Slots of this launch are
-// seg_slot - slot0 (>= 0 for multi-segment rows, seg_slot < 0 otherwise);
-// a slot and an output row are prod(ranks) doubles.
-extern "C" int splatt_hip_ttmc_segments_f64(
-    const int32_t * const * idx, const double * const * mats,
-    const int * ranks, int nother, const double * vals,
-    const int64_t * seg_start, const int32_t * seg_len,
-    const int32_t * seg_row, const int32_t * seg_slot, int64_t seg0,
-    int64_t nseg, int64_t slot0, double * ws, double * out, void * stream) {
+int ttmc_max_cols() { return MAX_COLS; }
+
+int ttmc_segments(const int32_t * const * idx, const double * const * mats,
+                  const int * ranks, int nother, const double * vals,
+                  const int64_t * seg_start, const int32_t * seg_len,
+                  const int32_t * seg_row, const int32_t * seg_slot,
+                  int64_t seg0, int64_t nseg, int64_t slot0, double * ws,
+                  double * out, void * stream) {
   if (nseg <= 0) return 0;
   if (nother < 2 || nother > 7 || nseg > 0x7FFFFFFF)
     return (int)hipErrorInvalidValue;
@@ -260,17 +260,17 @@ extern "C" int splatt_hip_ttmc_segments_f64(
 #undef LARGS
 }
 
-// multi-segment rows [m0, m0+nm): out[mrow[m]] = sum of slots
-// mslot[m]..mslot[m+1] (minus slot0), P doubles each
-extern "C" int splatt_hip_ttmc_reduce_f64(
-    const double * ws, const int32_t * mrow, const int64_t * mslot,
-    int64_t m0, int64_t nm, int64_t slot0, int P, double * out,
-    void * stream) {
+int ttmc_reduce(const double * ws, const int32_t * mrow,
+                const int64_t * mslot, int64_t m0, int64_t nm, int64_t slot0,
+                int P, double * out, void * stream) {
   if (nm <= 0) return 0;
   if (P < 1 || P > MAX_COLS || nm > 0x7FFFFFFF)
     return (int)hipErrorInvalidValue;
   dim3 grid((uint32_t)nm, (uint32_t)((P + 255) / 256)), block(256);
   hipLaunchKernelGGL(ttmc_reduce_kern, grid, block, 0, (hipStream_t)stream,
                      ws, mrow, mslot, m0, slot0, P, out);
-  return (int)hipGetLastError();
+  return launch_rc();
 }
+
+}  // namespace hip
+}  // namespace splatt

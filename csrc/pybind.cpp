@@ -1,11 +1,16 @@
 // Python boundary of the MI355X-native sparse tensor engine.
-// CPU core functions exposed over torch tensors; HIP kernel launchers are
-// declared extern "C" (defined in csrc/hip/*.hip, compiled by hipcc for
-// gfx950 and linked in) and take raw device pointers + the current stream,
-// so this translation unit needs no HIP headers.
+// CPU core functions exposed over torch tensors, and the HIP launchers of
+// csrc/hip/*.hip (compiled by hipcc for gfx950 and linked in). The launchers
+// are declared once, in csrc/hip/launchers.hpp, which both sides include;
+// they take raw device pointers + the current stream, so this translation
+// unit needs no HIP headers. Every gpu_* binding validates each tensor it
+// takes (check_dev: dtype, device, contiguity) before anything is launched,
+// picks the launcher instantiation with by_dtype / by_store, and turns the
+// launcher's return value into an exception with check_rc.
 #include <torch/extension.h>
-#include <vector>
+#include <array>
 #include <string>
+#include <vector>
 
 #include "core/types.hpp"
 #include "core/sptensor.hpp"
@@ -15,11 +20,47 @@
 #include "core/cpd.hpp"
 #include "core/io.hpp"
 #include "core/partition.hpp"
+#include "hip/launchers.hpp"
 
 namespace sp = splatt;
+namespace gpu = splatt::hip;
 using torch::Tensor;
 
 // ---------------------------------------------------------------- helpers
+
+// Element types travel as Tag<T> values into generic lambdas.
+template <typename T> struct Tag { using type = T; };
+#define TAG_TYPE(tag) typename decltype(tag)::type
+
+template <typename T>
+static constexpr torch::ScalarType dtype_of() {
+  if constexpr (std::is_same<T, gpu::bf16>::value) return torch::kBFloat16;
+  else return c10::CppTypeToScalarType<T>::value;
+}
+
+// f(Tag<float>) for f32, f(Tag<double>) otherwise
+template <typename F>
+static auto by_dtype(torch::ScalarType ty, F && f) {
+  return ty == torch::kFloat32 ? f(Tag<float>{}) : f(Tag<double>{});
+}
+template <typename F>
+static auto by_dtype(const Tensor & vals, F && f) {
+  return by_dtype(vals.scalar_type(), f);
+}
+
+// f(Tag<V>, Tag<S>): V from the values, S the factor storage type — V, or
+// f32 / bf16 under f64 values (reduced-precision factor STORAGE with f64
+// accumulation)
+template <typename F>
+static auto by_store(const Tensor & vals, const Tensor & mats0, F && f) {
+  if (vals.scalar_type() == torch::kFloat64) {
+    if (mats0.scalar_type() == torch::kFloat32)
+      return f(Tag<double>{}, Tag<float>{});
+    if (mats0.scalar_type() == torch::kBFloat16)
+      return f(Tag<double>{}, Tag<gpu::bf16>{});
+  }
+  return by_dtype(vals, [&](auto v) { return f(v, v); });
+}
 
 static sp::Options opts_from_dict(const py::dict & d) {
   sp::Options o;
@@ -61,10 +102,8 @@ static sp::SpTensor<V> coo_from_torch(const Tensor & inds, const Tensor & vals,
 template <typename V>
 static std::tuple<Tensor, Tensor, std::vector<int64_t>>
 coo_to_torch(const sp::SpTensor<V> & tt) {
-  const auto vopt = torch::TensorOptions().dtype(
-      std::is_same<V, double>::value ? torch::kFloat64 : torch::kFloat32);
   Tensor inds = torch::empty({tt.nmodes, (int64_t)tt.nnz}, torch::kInt64);
-  Tensor vals = torch::empty({(int64_t)tt.nnz}, vopt);
+  Tensor vals = torch::empty({(int64_t)tt.nnz}, dtype_of<V>());
   int64_t * ip = inds.data_ptr<int64_t>();
   V * vp = vals.data_ptr<V>();
   for (int m = 0; m < tt.nmodes; ++m)
@@ -79,8 +118,6 @@ coo_to_torch(const sp::SpTensor<V> & tt) {
 template <typename V>
 static py::dict csf_to_py(const sp::Csf<V> & c) {
   py::dict d;
-  const auto vopt = torch::TensorOptions().dtype(
-      std::is_same<V, double>::value ? torch::kFloat64 : torch::kFloat32);
   py::list fptr, fids;
   for (int l = 0; l < c.nmodes; ++l) {
     if (l < c.nmodes - 1) {
@@ -100,7 +137,7 @@ static py::dict csf_to_py(const sp::Csf<V> & c) {
       fids.append(t);
     }
   }
-  Tensor vals = torch::empty({(int64_t)c.vals.size()}, vopt);
+  Tensor vals = torch::empty({(int64_t)c.vals.size()}, dtype_of<V>());
   std::copy(c.vals.begin(), c.vals.end(), vals.data_ptr<V>());
   d["fptr"] = fptr;
   d["fids"] = fids;
@@ -150,193 +187,156 @@ static sp::Csf<V> csf_from_py(const py::dict & d) {
   return c;
 }
 
-#define DTYPE_DISPATCH(vals_dtype, fn)                                     \
-  ((vals_dtype) == torch::kFloat64 ? fn(double) : fn(float))
+// contiguous copies of the factors + their row pointers (CPU kernels)
+template <typename V>
+struct HostMats {
+  std::vector<Tensor> keep;
+  std::vector<const V *> ptr;
+  explicit HostMats(const std::vector<Tensor> & mats) {
+    for (auto & m : mats) {
+      keep.push_back(m.contiguous());
+      ptr.push_back(keep.back().data_ptr<V>());
+    }
+  }
+};
 
 // ---------------------------------------------------------------- io
 
 static py::object py_tensor_load(const std::string & path, const std::string & dtype) {
-  if (dtype == "f32") {
-    auto tt = sp::tensor_load<float>(path);
+  return by_dtype(dtype == "f32" ? torch::kFloat32 : torch::kFloat64,
+                  [&](auto tag) -> py::object {
+    auto tt = sp::tensor_load<TAG_TYPE(tag)>(path);
     auto [i, v, d] = coo_to_torch(tt);
     return py::make_tuple(i, v, d);
-  }
-  auto tt = sp::tensor_load<double>(path);
-  auto [i, v, d] = coo_to_torch(tt);
-  return py::make_tuple(i, v, d);
+  });
 }
 
 static void py_tns_write(const std::string & path, Tensor inds, Tensor vals,
                          std::vector<int64_t> dims) {
-  if (vals.scalar_type() == torch::kFloat32) {
-    auto tt = coo_from_torch<float>(inds, vals, dims);
-    sp::tns_write(tt, path);
-  } else {
-    auto tt = coo_from_torch<double>(inds, vals, dims);
-    sp::tns_write(tt, path);
-  }
+  by_dtype(vals, [&](auto tag) {
+    sp::tns_write(coo_from_torch<TAG_TYPE(tag)>(inds, vals, dims), path);
+  });
 }
 
 static void py_bin_write(const std::string & path, Tensor inds, Tensor vals,
                          std::vector<int64_t> dims, int idx_bytes, int val_bytes) {
-  if (vals.scalar_type() == torch::kFloat32) {
-    auto tt = coo_from_torch<float>(inds, vals, dims);
-    sp::bin_write(tt, path, idx_bytes, val_bytes);
-  } else {
-    auto tt = coo_from_torch<double>(inds, vals, dims);
-    sp::bin_write(tt, path, idx_bytes, val_bytes);
-  }
+  by_dtype(vals, [&](auto tag) {
+    sp::bin_write(coo_from_torch<TAG_TYPE(tag)>(inds, vals, dims), path,
+                  idx_bytes, val_bytes);
+  });
 }
 
 // ------------------------------------------------------------- coo utils
 
-template <typename V>
-static py::tuple py_coo_fix_t(Tensor inds, Tensor vals, std::vector<int64_t> dims,
-                              bool dedup, bool compress) {
-  auto tt = coo_from_torch<V>(inds, vals, dims);
-  int64_t ndups = 0, nempty = 0;
-  if (dedup) {
-    std::vector<int> perm(tt.nmodes);
-    for (int m = 0; m < tt.nmodes; ++m) perm[m] = m;
-    sp::coo_sort(tt, perm.data());
-    ndups = (int64_t)sp::coo_remove_dups(tt);
-  }
-  py::list indmaps;
-  if (compress) {
-    nempty = (int64_t)sp::coo_remove_empty(tt);
-    for (int m = 0; m < tt.nmodes; ++m) {
-      if (tt.indmap[m].empty()) {
-        indmaps.append(py::none());
-      } else {
-        Tensor t = torch::empty({(int64_t)tt.indmap[m].size()}, torch::kInt64);
-        std::copy(tt.indmap[m].begin(), tt.indmap[m].end(), t.data_ptr<int64_t>());
-        indmaps.append(t);
-      }
-    }
-  }
-  auto [i, v, d] = coo_to_torch(tt);
-  return py::make_tuple(i, v, d, ndups, nempty, indmaps);
-}
-
 static py::tuple py_coo_fix(Tensor inds, Tensor vals, std::vector<int64_t> dims,
                             bool dedup, bool compress) {
-  if (vals.scalar_type() == torch::kFloat32)
-    return py_coo_fix_t<float>(inds, vals, dims, dedup, compress);
-  return py_coo_fix_t<double>(inds, vals, dims, dedup, compress);
+  return by_dtype(vals, [&](auto tag) {
+    auto tt = coo_from_torch<TAG_TYPE(tag)>(inds, vals, dims);
+    int64_t ndups = 0, nempty = 0;
+    if (dedup) {
+      std::vector<int> perm(tt.nmodes);
+      for (int m = 0; m < tt.nmodes; ++m) perm[m] = m;
+      sp::coo_sort(tt, perm.data());
+      ndups = (int64_t)sp::coo_remove_dups(tt);
+    }
+    py::list indmaps;
+    if (compress) {
+      nempty = (int64_t)sp::coo_remove_empty(tt);
+      for (int m = 0; m < tt.nmodes; ++m) {
+        if (tt.indmap[m].empty()) {
+          indmaps.append(py::none());
+        } else {
+          Tensor t = torch::empty({(int64_t)tt.indmap[m].size()}, torch::kInt64);
+          std::copy(tt.indmap[m].begin(), tt.indmap[m].end(), t.data_ptr<int64_t>());
+          indmaps.append(t);
+        }
+      }
+    }
+    auto [i, v, d] = coo_to_torch(tt);
+    return py::make_tuple(i, v, d, ndups, nempty, indmaps);
+  });
 }
 
 // ------------------------------------------------------------- csf build
 
-template <typename V>
-static py::object py_csf_build_t(Tensor inds, Tensor vals,
-                                 std::vector<int64_t> dims,
-                                 std::vector<int64_t> perm) {
-  auto tt = coo_from_torch<V>(inds, vals, dims);
-  int p[sp::MAX_NMODES];
-  for (size_t i = 0; i < perm.size(); ++i) p[i] = (int)perm[i];
-  auto c = sp::csf_build(tt, p);
-  return csf_to_py(c);
-}
-
 static py::object py_csf_build(Tensor inds, Tensor vals,
                                std::vector<int64_t> dims,
                                std::vector<int64_t> perm) {
-  if (vals.scalar_type() == torch::kFloat32)
-    return py_csf_build_t<float>(inds, vals, dims, perm);
-  return py_csf_build_t<double>(inds, vals, dims, perm);
+  return by_dtype(vals, [&](auto tag) -> py::object {
+    auto tt = coo_from_torch<TAG_TYPE(tag)>(inds, vals, dims);
+    int p[sp::MAX_NMODES];
+    for (size_t i = 0; i < perm.size(); ++i) p[i] = (int)perm[i];
+    return csf_to_py(sp::csf_build(tt, p));
+  });
 }
 
 // ---------------------------------------------------------------- mttkrp
 
-template <typename V>
-static Tensor py_mttkrp_stream_t(Tensor inds, Tensor vals,
-                                 std::vector<int64_t> dims,
-                                 std::vector<Tensor> mats, int mode) {
-  auto tt = coo_from_torch<V>(inds, vals, dims);
-  const int F = (int)mats[0].size(1);
-  std::vector<const V*> mp;
-  std::vector<Tensor> mc;
-  for (auto & m : mats) { mc.push_back(m.contiguous()); mp.push_back(mc.back().data_ptr<V>()); }
-  Tensor out = torch::empty({dims[mode], F}, mats[0].options());
-  sp::mttkrp_stream(tt, mp.data(), out.data_ptr<V>(), mode, F);
-  return out;
-}
-
 static Tensor py_mttkrp_stream(Tensor inds, Tensor vals, std::vector<int64_t> dims,
                                std::vector<Tensor> mats, int mode) {
-  if (vals.scalar_type() == torch::kFloat32)
-    return py_mttkrp_stream_t<float>(inds, vals, dims, mats, mode);
-  return py_mttkrp_stream_t<double>(inds, vals, dims, mats, mode);
-}
-
-template <typename V>
-static Tensor py_mttkrp_csf_t(py::dict csf, std::vector<Tensor> mats, int mode,
-                              int nthreads) {
-  auto c = csf_from_py<V>(csf);
-  const int F = (int)mats[0].size(1);
-  std::vector<const V*> mp;
-  std::vector<Tensor> mc;
-  for (auto & m : mats) { mc.push_back(m.contiguous()); mp.push_back(mc.back().data_ptr<V>()); }
-  Tensor out = torch::empty({(int64_t)c.dims[mode], F}, mats[0].options());
-  sp::mttkrp_csf_cpu(c, mp.data(), out.data_ptr<V>(), mode, F, nthreads);
-  return out;
+  return by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    auto tt = coo_from_torch<V>(inds, vals, dims);
+    const int F = (int)mats[0].size(1);
+    HostMats<V> hm(mats);
+    Tensor out = torch::empty({dims[mode], F}, mats[0].options());
+    sp::mttkrp_stream(tt, hm.ptr.data(), out.data_ptr<V>(), mode, F);
+    return out;
+  });
 }
 
 static Tensor py_mttkrp_csf(py::dict csf, std::vector<Tensor> mats, int mode,
                             int nthreads) {
-  if (mats[0].scalar_type() == torch::kFloat32)
-    return py_mttkrp_csf_t<float>(csf, mats, mode, nthreads);
-  return py_mttkrp_csf_t<double>(csf, mats, mode, nthreads);
+  return by_dtype(mats[0], [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    auto c = csf_from_py<V>(csf);
+    const int F = (int)mats[0].size(1);
+    HostMats<V> hm(mats);
+    Tensor out = torch::empty({(int64_t)c.dims[mode], F}, mats[0].options());
+    sp::mttkrp_csf_cpu(c, hm.ptr.data(), out.data_ptr<V>(), mode, F, nthreads);
+    return out;
+  });
 }
 
 // ------------------------------------------------------------------- cpd
 
-template <typename V>
-static py::dict py_cpd_als_t(Tensor inds, Tensor vals, std::vector<int64_t> dims,
-                             int rank, py::dict opts) {
-  auto o = opts_from_dict(opts);
-  auto tt = coo_from_torch<V>(inds, vals, dims);
-  auto set = sp::csf_alloc(tt, o);
-  auto k = sp::cpd_als(set, rank, o);
-  py::dict r;
-  py::list factors;
-  const auto vopt = torch::TensorOptions().dtype(
-      std::is_same<V, double>::value ? torch::kFloat64 : torch::kFloat32);
-  for (int m = 0; m < k.nmodes; ++m) {
-    Tensor t = torch::empty({(int64_t)k.dims[m], rank}, vopt);
-    std::copy(k.factors[m].begin(), k.factors[m].end(), t.data_ptr<V>());
-    factors.append(t);
-  }
-  Tensor lam = torch::empty({rank}, vopt);
-  std::copy(k.lambda.begin(), k.lambda.end(), lam.data_ptr<V>());
-  r["factors"] = factors;
-  r["lambda"] = lam;
-  r["fit"] = k.fit;
-  r["niters"] = k.niters;
-  return r;
-}
-
 static py::dict py_cpd_als(Tensor inds, Tensor vals, std::vector<int64_t> dims,
                            int rank, py::dict opts) {
-  if (vals.scalar_type() == torch::kFloat32)
-    return py_cpd_als_t<float>(inds, vals, dims, rank, opts);
-  return py_cpd_als_t<double>(inds, vals, dims, rank, opts);
+  return by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    auto o = opts_from_dict(opts);
+    auto tt = coo_from_torch<V>(inds, vals, dims);
+    auto set = sp::csf_alloc(tt, o);
+    auto k = sp::cpd_als(set, rank, o);
+    py::dict r;
+    py::list factors;
+    for (int m = 0; m < k.nmodes; ++m) {
+      Tensor t = torch::empty({(int64_t)k.dims[m], rank}, dtype_of<V>());
+      std::copy(k.factors[m].begin(), k.factors[m].end(), t.data_ptr<V>());
+      factors.append(t);
+    }
+    Tensor lam = torch::empty({rank}, dtype_of<V>());
+    std::copy(k.lambda.begin(), k.lambda.end(), lam.data_ptr<V>());
+    r["factors"] = factors;
+    r["lambda"] = lam;
+    r["fit"] = k.fit;
+    r["niters"] = k.niters;
+    return r;
+  });
 }
 
 // --------------------------------------------------------------- dense ops
 
 static Tensor py_seeded_init(int64_t nrows, int rank, int64_t row0,
                              uint64_t seed, int mode, const std::string & dtype) {
-  if (dtype == "f32") {
-    Tensor t = torch::empty({nrows, rank}, torch::kFloat32);
-    sp::seeded_factor_init(t.data_ptr<float>(), (sp::idx_t)nrows, rank,
+  return by_dtype(dtype == "f32" ? torch::kFloat32 : torch::kFloat64,
+                  [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    Tensor t = torch::empty({nrows, rank}, dtype_of<V>());
+    sp::seeded_factor_init(t.data_ptr<V>(), (sp::idx_t)nrows, rank,
                            (sp::idx_t)row0, seed, mode);
     return t;
-  }
-  Tensor t = torch::empty({nrows, rank}, torch::kFloat64);
-  sp::seeded_factor_init(t.data_ptr<double>(), (sp::idx_t)nrows, rank,
-                         (sp::idx_t)row0, seed, mode);
-  return t;
+  });
 }
 
 static std::vector<int64_t> py_order_modes(std::vector<int64_t> dims,
@@ -351,355 +351,195 @@ static std::vector<int64_t> py_order_modes(std::vector<int64_t> dims,
   return std::vector<int64_t>(p, p + nm);
 }
 
-// --------------------------------------------------- HIP launcher externs
+// ------------------------------------------------- HIP launcher plumbing
+// Python passes device tensors + the current stream's handle.
 
-extern "C" {
-// defined in csrc/hip/mttkrp_kernels.hip (gfx950); stream is hipStream_t
-void splatt_hip_mttkrp_root3_f64(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const double* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const double* A1, const double* A2, double* out, int rank, void* stream);
-void splatt_hip_mttkrp_root3_f32(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const float* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const float* A1, const float* A2, float* out, int rank, void* stream);
-void splatt_hip_mttkrp_intl3_f64(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const double* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const double* A0, const double* A2, double* out, int rank, void* stream);
-void splatt_hip_mttkrp_intl3_f32(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const float* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const float* A0, const float* A2, float* out, int rank, void* stream);
-void splatt_hip_mttkrp_leaf3_f64(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const double* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const double* A0, const double* A1, double* out, int rank, void* stream);
-void splatt_hip_mttkrp_leaf3_f32(
-    const int64_t* fptr0, const int32_t* fids0, const int64_t* fptr1,
-    const int32_t* fids1, const int32_t* fids2, const float* vals,
-    int64_t nslices, int64_t nfibs, int64_t nnz,
-    const float* A0, const float* A1, float* out, int rank, void* stream);
-int splatt_hip_kernels_arch(void);
-// flat (expanded-CSF) kernels, csrc/hip/mttkrp_flat.hip
-void splatt_hip_mttkrp_flat_f64(
-    const int32_t*, const int32_t* const*, const double* const*,
-    const double*, int64_t, double*, int, int, void*);
-void splatt_hip_mttkrp_flat_f32(
-    const int32_t*, const int32_t* const*, const float* const*,
-    const float*, int64_t, float*, int, int, void*);
-// row-pointer variants (root output of a key-sorted stream); -1 = declined
-int splatt_hip_mttkrp_flat_rp_f64(
-    const int64_t*, int64_t, int64_t, const int32_t* const*,
-    const double* const*, const double*, int64_t, double*, int, int, void*);
-int splatt_hip_mttkrp_flat_rp_f32(
-    const int64_t*, int64_t, int64_t, const int32_t* const*,
-    const float* const*, const float*, int64_t, float*, int, int, void*);
-int splatt_hip_mttkrp_flat_rp_f64f32(
-    const int64_t*, int64_t, int64_t, const int32_t* const*,
-    const float* const*, const double*, int64_t, double*, int, int, void*);
-int splatt_hip_mttkrp_flat_rp_f64bf16(
-    const int64_t*, int64_t, int64_t, const int32_t* const*,
-    const uint16_t* const*, const double*, int64_t, double*, int, int, void*);
-// f32 value stream (f64 factors/output), v7 only; -1 = declined
-int splatt_hip_mttkrp_flat_rp_f64v32(
-    const int64_t*, int64_t, int64_t, const int32_t* const*,
-    const double* const*, const float*, int64_t, double*, int, int, void*);
-int splatt_hip_mttkrp_flat_f64v32(
-    const int32_t*, const int32_t* const*, const double* const*,
-    const float*, int64_t, double*, int, int, void*);
-// deterministic flat kernel, csrc/hip/mttkrp_det.hip
-int64_t splatt_hip_flat_det_ws(int64_t, int);
-int splatt_hip_mttkrp_flat_det_f64(
-    const int32_t*, const int32_t* const*, const double* const*,
-    const double*, int64_t, double*, double*, int64_t, int, int, void*);
-int splatt_hip_mttkrp_flat_det_f32(
-    const int32_t*, const int32_t* const*, const float* const*,
-    const float*, int64_t, float*, float*, int64_t, int, int, void*);
-// dense kernels, csrc/hip/dense_kernels.hip
-int splatt_hip_rowsolve_f64(const double*, const double*, double*, int64_t,
-                            int, void*);
-void splatt_hip_gram_det_f64(const double*, int64_t, int, double*, int64_t,
-                             double*, void*);
-void splatt_hip_gram_det_f32(const float*, int64_t, int, float*, int64_t,
-                             float*, void*);
-int splatt_hip_rowsolve_f32(const float*, const float*, float*, int64_t,
-                            int, void*);
-void splatt_hip_gram_f64(const double*, int64_t, int, double*, void*);
-void splatt_hip_gram_f32(const float*, int64_t, int, float*, void*);
-void splatt_hip_spd_inverse_f64(const double*, double*, int, void*);
-void splatt_hip_spd_inverse_f32(const float*, float*, int, void*);
-void splatt_hip_colacc_f64(const double*, int64_t, int, int, double*, void*);
-void splatt_hip_colscale_f64(double*, int64_t, int, const double*, void*);
-void splatt_hip_coldot_f64(const double*, const double*, int64_t, int,
-                           double*, void*);
-// LDS-staged flat kernel, csrc/hip/mttkrp_lds.hip
-void splatt_hip_mttkrp_flat5_f64(
-    const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-    const int32_t*, const double*, const double*, const double*,
-    const double*, const double*, const int64_t*, const int64_t*,
-    const int32_t*, int64_t, int32_t, int32_t, double*, int, int, void*);
-void splatt_hip_mttkrp_flat5_f32(
-    const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-    const int32_t*, const float*, const float*, const float*,
-    const float*, const float*, const int64_t*, const int64_t*,
-    const int32_t*, int64_t, int32_t, int32_t, float*, int, int, void*);
-void splatt_hip_mttkrp_flat6_f64(
-    const int32_t*, const double*, const double*, const double*,
-    const double*, const int64_t*, const int64_t*, const int32_t*, int64_t,
-    int32_t, int32_t, double*, int, int, void*);
-void splatt_hip_mttkrp_flat6_f32(
-    const int32_t*, const float*, const float*, const float*,
-    const float*, const int64_t*, const int64_t*, const int32_t*, int64_t,
-    int32_t, int32_t, float*, int, int, void*);
-int splatt_hip_mttkrp_flat_f64f32(
-    const int32_t*, const int32_t* const*, const float* const*,
-    const double*, int64_t, double*, int, int, void*);
-int splatt_hip_mttkrp_flat_f64bf16(
-    const int32_t*, const int32_t* const*, const uint16_t* const*,
-    const double*, int64_t, double*, int, int, void*);
-void splatt_hip_mttkrp_flat6_f64f32(
-    const int32_t*, const float*, const float*, const float*,
-    const double*, const int64_t*, const int64_t*, const int32_t*, int64_t,
-    int32_t, int32_t, double*, int, int, void*);
-void splatt_hip_mttkrp_flat6_f64bf16(
-    const int32_t*, const uint16_t*, const uint16_t*, const uint16_t*,
-    const double*, const int64_t*, const int64_t*, const int32_t*, int64_t,
-    int32_t, int32_t, double*, int, int, void*);
+static void check_dev(const Tensor & t, torch::ScalarType ty,
+                      const char * name) {
+  TORCH_CHECK(t.scalar_type() == ty, name, " has dtype ", t.scalar_type(),
+              ", expected ", ty);
+  TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-// LDS-staged variant: idx[0]/mats[0] is the bucketed level; block
-// descriptors carry (nnz range, bucket row0)
-static void py_gpu_mttkrp_flat5(Tensor key, std::vector<Tensor> idx,
-                                std::vector<Tensor> mats, Tensor vals,
-                                Tensor blk_start, Tensor blk_end,
-                                Tensor blk_row0, int64_t chunk, int64_t dim0,
-                                Tensor out, int64_t stream) {
-  const int nother = (int)idx.size();
-  TORCH_CHECK(nother >= 2 && nother <= 4);
-  const int rank = (int)mats[0].size(1);
-  const int32_t * ip[4] = {nullptr, nullptr, nullptr, nullptr};
-  for (int t = 0; t < nother; ++t) ip[t] = idx[t].data_ptr<int32_t>();
-  const int64_t nblocks = blk_start.numel();
-  if (vals.scalar_type() == torch::kFloat64) {
-    const double * mp[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    splatt_hip_mttkrp_flat5_f64(key.data_ptr<int32_t>(), ip[0], ip[1], ip[2],
-                                ip[3], mp[0], mp[1], mp[2], mp[3],
-                                vals.data_ptr<double>(),
-                                blk_start.data_ptr<int64_t>(),
-                                blk_end.data_ptr<int64_t>(),
-                                blk_row0.data_ptr<int32_t>(), nblocks,
-                                (int32_t)chunk, (int32_t)dim0,
-                                out.data_ptr<double>(), rank, nother,
-                                (void*)stream);
-  } else {
-    const float * mp[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-    splatt_hip_mttkrp_flat5_f32(key.data_ptr<int32_t>(), ip[0], ip[1], ip[2],
-                                ip[3], mp[0], mp[1], mp[2], mp[3],
-                                vals.data_ptr<float>(),
-                                blk_start.data_ptr<int64_t>(),
-                                blk_end.data_ptr<int64_t>(),
-                                blk_row0.data_ptr<int32_t>(), nblocks,
-                                (int32_t)chunk, (int32_t)dim0,
-                                out.data_ptr<float>(), rank, nother,
-                                (void*)stream);
+// device pointer of a checked tensor; the one place a bf16 tensor becomes
+// the launchers' bf16
+template <typename T>
+static T * dev_ptr(const Tensor & t, const char * name) {
+  check_dev(t, dtype_of<T>(), name);
+  if constexpr (std::is_same<T, gpu::bf16>::value)
+    return reinterpret_cast<gpu::bf16 *>(t.data_ptr<at::BFloat16>());
+  else
+    return t.data_ptr<T>();
+}
+
+// Host table of the device pointers of tensors[0, n), each checked; always
+// 8 entries, the unused ones null, as the launchers expect.
+template <typename T>
+static std::array<const T *, 8> ptr_table(const std::vector<Tensor> & tensors,
+                                          size_t n, const char * name) {
+  TORCH_CHECK(n <= 8 && tensors.size() == n, "expected ", n, " ", name,
+              " tensors, got ", tensors.size());
+  std::array<const T *, 8> tab{};
+  for (size_t t = 0; t < n; ++t) tab[t] = dev_ptr<T>(tensors[t], name);
+  return tab;
+}
+
+// the per-nonzero int32 index streams of a launch: nnz entries each
+static std::array<const int32_t *, 8> stream_table(
+    const std::vector<Tensor> & idx, size_t n, int64_t nnz) {
+  auto tab = ptr_table<int32_t>(idx, n, "idx");
+  for (auto & i : idx)
+    TORCH_CHECK(i.numel() == nnz, "index stream length != nnz");
+  return tab;
+}
+
+// the factor matrices of a launch: [rows, rank] each
+template <typename S>
+static std::array<const S *, 8> factor_table(const std::vector<Tensor> & mats,
+                                             size_t n, int64_t rank) {
+  auto tab = ptr_table<S>(mats, n, "factor");
+  for (auto & m : mats)
+    TORCH_CHECK(m.dim() == 2 && m.size(1) == rank, "factor rank mismatch");
+  return tab;
+}
+
+// rank of a launch = columns of its first factor
+static int rank_of(const std::vector<Tensor> & mats) {
+  TORCH_CHECK(!mats.empty() && mats[0].dim() == 2, "factors must be 2-D");
+  return (int)mats[0].size(1);
+}
+
+// `out` of an MTTKRP: [rows, rank]
+template <typename V>
+static V * out_ptr(const Tensor & out, int rank) {
+  V * p = dev_ptr<V>(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == rank,
+              "out must be [rows, rank]");
+  return p;
+}
+
+// A launcher's return value (launchers.hpp) as an exception: positive = the
+// launch's hipError_t, negative = declined, with the binding's message.
+static void check_rc(int rc, const char * what, const std::string & declined) {
+  TORCH_CHECK(rc <= 0, what, " kernel launch failed: ", gpu::error_string(rc));
+  TORCH_CHECK(rc == 0, declined);
+}
+// for launchers that never decline
+static void check_rc(int rc, const char * what) {
+  check_rc(rc, what, std::string(what) + " launcher declined");
+}
+
+// block descriptors of the LDS-staged kernels (mttkrp.py _stage_blocks)
+struct StageBlocks {
+  const int64_t * start, * end;
+  const int32_t * row0;
+  int64_t n;
+  StageBlocks(const Tensor & blk_start, const Tensor & blk_end,
+              const Tensor & blk_row0)
+      : start(dev_ptr<int64_t>(blk_start, "blk_start")),
+        end(dev_ptr<int64_t>(blk_end, "blk_end")),
+        row0(dev_ptr<int32_t>(blk_row0, "blk_row0")), n(blk_start.numel()) {
+    TORCH_CHECK(blk_end.numel() == n && blk_row0.numel() == n,
+                "block descriptor lengths differ");
   }
-}
+};
 
-extern "C" {
-int splatt_hip_mttkrp_det6_f64(
-    const int32_t*, const double*, const double*, const double*,
-    const double*, const int64_t*, const int64_t*, const int32_t*,
-    const int64_t*, int64_t,
-    int32_t, int32_t, int64_t, int64_t, double*, double*, double*, int,
-    int, void*);
-int splatt_hip_mttkrp_det6_f32(
-    const int32_t*, const float*, const float*, const float*,
-    const float*, const int64_t*, const int64_t*, const int32_t*,
-    const int64_t*, int64_t,
-    int32_t, int32_t, int64_t, int64_t, float*, float*, float*, int, int,
-    void*);
-}
-
-// LDS-staged bitwise-deterministic MTTKRP over the packed stream:
-// per-bucket privatized outputs + ordered fixup + ascending-bucket fold
-static void py_gpu_mttkrp_det6(Tensor pack, std::vector<Tensor> mats,
-                               Tensor vals, Tensor blk_start,
-                               Tensor blk_end, Tensor blk_row0,
-                               Tensor blk_bucket_p0,
-                               int64_t chunk, int64_t dim0,
-                               int64_t nbuckets, Tensor outb, Tensor side,
-                               Tensor out, int64_t stream) {
-  const int nother = (int)mats.size();
-  TORCH_CHECK(nother >= 2 && nother <= 3);
-  TORCH_CHECK(pack.is_contiguous() && pack.size(1) == 4
-              && pack.scalar_type() == torch::kInt32);
-  const int rank = (int)mats[0].size(1);
-  const int64_t nblocks = blk_start.numel();
-  const int64_t nrows_out = out.size(0);
-  int rc;
-  if (vals.scalar_type() == torch::kFloat64) {
-    const double * mp[3] = {nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    rc = splatt_hip_mttkrp_det6_f64(
-        pack.data_ptr<int32_t>(), mp[0], mp[1], mp[2],
-        vals.data_ptr<double>(), blk_start.data_ptr<int64_t>(),
-        blk_end.data_ptr<int64_t>(), blk_row0.data_ptr<int32_t>(),
-        blk_bucket_p0.data_ptr<int64_t>(), nblocks,
-        (int32_t)chunk, (int32_t)dim0, nrows_out, nbuckets,
-        outb.data_ptr<double>(), side.data_ptr<double>(),
-        out.data_ptr<double>(), rank, nother, (void*)stream);
-  } else {
-    const float * mp[3] = {nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-    rc = splatt_hip_mttkrp_det6_f32(
-        pack.data_ptr<int32_t>(), mp[0], mp[1], mp[2],
-        vals.data_ptr<float>(), blk_start.data_ptr<int64_t>(),
-        blk_end.data_ptr<int64_t>(), blk_row0.data_ptr<int32_t>(),
-        blk_bucket_p0.data_ptr<int64_t>(), nblocks,
-        (int32_t)chunk, (int32_t)dim0, nrows_out, nbuckets,
-        outb.data_ptr<float>(), side.data_ptr<float>(),
-        out.data_ptr<float>(), rank, nother, (void*)stream);
-  }
-  TORCH_CHECK(rc == 0, "det6 supports spec ranks and 3-4 modes, rc=", rc);
-}
-
-// packed-stream LDS variant: one int4 word per nonzero
-// (x = output key, y = staged level, z/w = remaining levels)
-static void py_gpu_mttkrp_flat6(Tensor pack, std::vector<Tensor> mats,
-                                Tensor vals, Tensor blk_start,
-                                Tensor blk_end, Tensor blk_row0,
-                                int64_t chunk, int64_t dim0, Tensor out,
-                                int64_t stream) {
-  const int nother = (int)mats.size();
-  TORCH_CHECK(nother >= 2 && nother <= 3);
-  TORCH_CHECK(pack.is_contiguous() && pack.size(1) == 4
+// the packed stream of flat6 / det6: one int4 word per nonzero
+static const int32_t * pack_ptr(const Tensor & pack, int64_t nnz) {
+  TORCH_CHECK(pack.dim() == 2 && pack.size(1) == 4 && pack.is_contiguous()
               && pack.scalar_type() == torch::kInt32,
               "pack must be contiguous [nnz,4] int32");
-  const int rank = (int)mats[0].size(1);
-  const int64_t nblocks = blk_start.numel();
-  if (vals.scalar_type() == torch::kFloat64) {
-    // reduced-precision factor STORAGE with f64 accumulation
-    if (mats[0].scalar_type() == torch::kFloat32) {
-      const float * mp[3] = {nullptr, nullptr, nullptr};
-      for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-      splatt_hip_mttkrp_flat6_f64f32(pack.data_ptr<int32_t>(), mp[0], mp[1],
-                                     mp[2], vals.data_ptr<double>(),
-                                     blk_start.data_ptr<int64_t>(),
-                                     blk_end.data_ptr<int64_t>(),
-                                     blk_row0.data_ptr<int32_t>(), nblocks,
-                                     (int32_t)chunk, (int32_t)dim0,
-                                     out.data_ptr<double>(), rank, nother,
-                                     (void*)stream);
-      return;
-    }
-    if (mats[0].scalar_type() == torch::kBFloat16) {
-      const uint16_t * mp[3] = {nullptr, nullptr, nullptr};
-      for (int t = 0; t < nother; ++t)
-        mp[t] = reinterpret_cast<const uint16_t*>(
-            mats[t].data_ptr<at::BFloat16>());
-      splatt_hip_mttkrp_flat6_f64bf16(pack.data_ptr<int32_t>(), mp[0],
-                                      mp[1], mp[2], vals.data_ptr<double>(),
-                                      blk_start.data_ptr<int64_t>(),
-                                      blk_end.data_ptr<int64_t>(),
-                                      blk_row0.data_ptr<int32_t>(), nblocks,
-                                      (int32_t)chunk, (int32_t)dim0,
-                                      out.data_ptr<double>(), rank, nother,
-                                      (void*)stream);
-      return;
-    }
-    const double * mp[3] = {nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    splatt_hip_mttkrp_flat6_f64(pack.data_ptr<int32_t>(), mp[0], mp[1],
-                                mp[2], vals.data_ptr<double>(),
-                                blk_start.data_ptr<int64_t>(),
-                                blk_end.data_ptr<int64_t>(),
-                                blk_row0.data_ptr<int32_t>(), nblocks,
-                                (int32_t)chunk, (int32_t)dim0,
-                                out.data_ptr<double>(), rank, nother,
-                                (void*)stream);
-  } else {
-    const float * mp[3] = {nullptr, nullptr, nullptr};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-    splatt_hip_mttkrp_flat6_f32(pack.data_ptr<int32_t>(), mp[0], mp[1],
-                                mp[2], vals.data_ptr<float>(),
-                                blk_start.data_ptr<int64_t>(),
-                                blk_end.data_ptr<int64_t>(),
-                                blk_row0.data_ptr<int32_t>(), nblocks,
-                                (int32_t)chunk, (int32_t)dim0,
-                                out.data_ptr<float>(), rank, nother,
-                                (void*)stream);
-  }
+  const int32_t * p = dev_ptr<int32_t>(pack, "pack");
+  TORCH_CHECK(pack.size(0) == nnz, "pack length != nnz");
+  return p;
 }
 
-// G (FxF, pre-zeroed) += A^T A for tall-skinny device A
-static void py_gpu_gram(Tensor A, Tensor G, int64_t stream) {
-  const int64_t n = A.size(0);
-  const int F = (int)A.size(1);
-  if (A.scalar_type() == torch::kFloat64)
-    splatt_hip_gram_f64(A.data_ptr<double>(), n, F, G.data_ptr<double>(),
-                        (void*)stream);
-  else
-    splatt_hip_gram_f32(A.data_ptr<float>(), n, F, G.data_ptr<float>(),
-                        (void*)stream);
+static const int64_t * rowptr_ptr(const Tensor & rowptr, const Tensor & out) {
+  const int64_t * p = dev_ptr<int64_t>(rowptr, "rowptr");
+  TORCH_CHECK(rowptr.numel() >= 2 && out.dim() == 2
+              && rowptr.numel() <= out.size(0) + 1,
+              "rowptr must be contiguous int64 with at most rows + 1 entries");
+  return p;
+}
+
+// ------------------------------------------------------------ MTTKRP (HIP)
+
+// 3-mode CSF walk; which: 0 root, 1 internal, 2 leaf output
+static void py_gpu_mttkrp3(int which, Tensor fptr0, py::object fids0, Tensor fptr1,
+                           Tensor fids1, Tensor fids2, Tensor vals,
+                           Tensor Ma, Tensor Mb, Tensor out, int64_t stream) {
+  TORCH_CHECK(which >= 0 && which <= 2, "which: 0 root, 1 internal, 2 leaf");
+  by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const int64_t * fp0 = dev_ptr<int64_t>(fptr0, "fptr0");
+    const int32_t * f0 = fids0.is_none() ? nullptr
+                         : dev_ptr<int32_t>(fids0.cast<Tensor>(), "fids0");
+    const int64_t * fp1 = dev_ptr<int64_t>(fptr1, "fptr1");
+    const int32_t * fi1 = dev_ptr<int32_t>(fids1, "fids1");
+    const int32_t * fi2 = dev_ptr<int32_t>(fids2, "fids2");
+    const V * vp = dev_ptr<V>(vals, "vals");
+    const V * a = dev_ptr<V>(Ma, "Ma");
+    const V * b = dev_ptr<V>(Mb, "Mb");
+    const int64_t nslices = fptr0.numel() - 1;
+    const int64_t nfibs = fptr1.numel() - 1;
+    const int64_t nnz = vals.numel();
+    TORCH_CHECK(fids1.numel() == nfibs && fids2.numel() == nnz,
+                "fids1/fids2 lengths != fibers/nnz");
+    TORCH_CHECK(Ma.dim() == 2 && Mb.dim() == 2 && Mb.size(1) == Ma.size(1),
+                "factor rank mismatch");
+    const int rank = (int)Ma.size(1);
+    check_rc(gpu::mttkrp_csf3<V>(which, fp0, f0, fp1, fi1, fi2, vp, nslices,
+                                 nfibs, nnz, a, b, out_ptr<V>(out, rank),
+                                 rank, (void *)stream), "mttkrp3");
+  });
+}
+
+// The key-stream / row-pointer forms of the flat kernel share this: exactly
+// one of key / rowptr is given. Returns the launcher's return value.
+template <typename V, typename S, typename VS>
+static int flat_launch(const c10::optional<Tensor> & rowptr, int64_t p0,
+                       const c10::optional<Tensor> & key,
+                       const std::vector<Tensor> & idx,
+                       const std::vector<Tensor> & mats, const Tensor & vals,
+                       const Tensor & out, int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
+  TORCH_CHECK(rowptr.has_value() != key.has_value(),
+              "pass row pointers or a key stream, not both");
+  const VS * vp = dev_ptr<VS>(vals, "vals");
+  const int64_t nnz = vals.numel();
+  const int rank = rank_of(mats);
+  V * op = out_ptr<V>(out, rank);
+  auto ip = stream_table(idx, nother, nnz);
+  auto mp = factor_table<S>(mats, nother, rank);
+  const int32_t * kp = nullptr;
+  const int64_t * rp = nullptr;
+  if (key.has_value()) {
+    kp = dev_ptr<int32_t>(*key, "key");
+    TORCH_CHECK(key->numel() == nnz, "key must be int32 of nnz entries");
+  } else {
+    rp = rowptr_ptr(*rowptr, out);
+  }
+  return gpu::mttkrp_flat<V, S, VS>(kp, rp, rp ? rowptr->numel() - 1 : 0, p0,
+                                    ip.data(), mp.data(), vp, nnz, op, rank,
+                                    (int)nother, (void *)stream);
 }
 
 // key + per-other-level (idx, mat) pairs; nnz products folded by key runs
 static void py_gpu_mttkrp_flat(Tensor key, std::vector<Tensor> idx,
                                std::vector<Tensor> mats, Tensor vals,
                                Tensor out, int64_t stream) {
-  const int nother = (int)idx.size();
-  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
-  TORCH_CHECK((int)mats.size() == nother);
-  const int rank = (int)mats[0].size(1);
-  const int64_t nnz = vals.numel();
-  const int32_t * ip[8] = {};
-  for (int t = 0; t < nother; ++t) ip[t] = idx[t].data_ptr<int32_t>();
-  if (vals.scalar_type() == torch::kFloat64) {
-    // reduced-precision factor STORAGE with f64 accumulation (v2 path)
-    if (mats[0].scalar_type() == torch::kFloat32) {
-      const float * mp[8] = {};
-      for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-      TORCH_CHECK(splatt_hip_mttkrp_flat_f64f32(
-                      key.data_ptr<int32_t>(), ip, mp,
-                      vals.data_ptr<double>(), nnz, out.data_ptr<double>(),
-                      rank, nother, (void*)stream) == 0,
-                  "f32 factor store needs rank in {4,8,16,32,64}");
-      return;
-    }
-    if (mats[0].scalar_type() == torch::kBFloat16) {
-      const uint16_t * mp[8] = {};
-      for (int t = 0; t < nother; ++t)
-        mp[t] = reinterpret_cast<const uint16_t*>(
-            mats[t].data_ptr<at::BFloat16>());
-      TORCH_CHECK(splatt_hip_mttkrp_flat_f64bf16(
-                      key.data_ptr<int32_t>(), ip, mp,
-                      vals.data_ptr<double>(), nnz, out.data_ptr<double>(),
-                      rank, nother, (void*)stream) == 0,
-                  "bf16 factor store needs rank in {4,8,16,32,64}");
-      return;
-    }
-    const double * mp[8] = {};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    splatt_hip_mttkrp_flat_f64(key.data_ptr<int32_t>(), ip, mp,
-                               vals.data_ptr<double>(), nnz,
-                               out.data_ptr<double>(), rank, nother,
-                               (void*)stream);
-  } else {
-    const float * mp[8] = {};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-    splatt_hip_mttkrp_flat_f32(key.data_ptr<int32_t>(), ip, mp,
-                               vals.data_ptr<float>(), nnz,
-                               out.data_ptr<float>(), rank, nother,
-                               (void*)stream);
-  }
+  TORCH_CHECK(!mats.empty(), "flat kernel supports 3..8 modes");
+  by_store(vals, mats[0], [&](auto v, auto s) {
+    using V = TAG_TYPE(v);
+    using S = TAG_TYPE(s);
+    const int rc = flat_launch<V, S, V>(c10::nullopt, 0, key, idx, mats, vals,
+                                        out, stream);
+    check_rc(rc, "flat MTTKRP",
+             std::string(std::is_same<S, float>::value ? "f32" : "bf16")
+             + " factor store needs rank in {4,8,16,32,64}");
+  });
 }
 
 // Row-pointer form of the flat kernel: `rowptr` (int64, rows + 1 global
@@ -710,46 +550,15 @@ static bool py_gpu_mttkrp_flat_rp(Tensor rowptr, int64_t p0,
                                   std::vector<Tensor> idx,
                                   std::vector<Tensor> mats, Tensor vals,
                                   Tensor out, int64_t stream) {
-  const int nother = (int)idx.size();
-  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
-  TORCH_CHECK((int)mats.size() == nother);
-  TORCH_CHECK(rowptr.scalar_type() == torch::kInt64 && rowptr.is_contiguous()
-              && rowptr.numel() >= 2 && rowptr.numel() <= out.size(0) + 1,
-              "rowptr must be contiguous int64 with at most rows + 1 entries");
-  const int rank = (int)mats[0].size(1);
-  const int64_t nnz = vals.numel();
-  const int64_t nrows = rowptr.numel() - 1;
-  const int64_t * rp = rowptr.data_ptr<int64_t>();
-  const int32_t * ip[8] = {};
-  for (int t = 0; t < nother; ++t) ip[t] = idx[t].data_ptr<int32_t>();
-  if (vals.scalar_type() == torch::kFloat64) {
-    if (mats[0].scalar_type() == torch::kFloat32) {
-      const float * mp[8] = {};
-      for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-      return splatt_hip_mttkrp_flat_rp_f64f32(
-                 rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
-                 out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
-    }
-    if (mats[0].scalar_type() == torch::kBFloat16) {
-      const uint16_t * mp[8] = {};
-      for (int t = 0; t < nother; ++t)
-        mp[t] = reinterpret_cast<const uint16_t*>(
-            mats[t].data_ptr<at::BFloat16>());
-      return splatt_hip_mttkrp_flat_rp_f64bf16(
-                 rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
-                 out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
-    }
-    const double * mp[8] = {};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    return splatt_hip_mttkrp_flat_rp_f64(
-               rp, nrows, p0, ip, mp, vals.data_ptr<double>(), nnz,
-               out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
-  }
-  const float * mp[8] = {};
-  for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-  return splatt_hip_mttkrp_flat_rp_f32(
-             rp, nrows, p0, ip, mp, vals.data_ptr<float>(), nnz,
-             out.data_ptr<float>(), rank, nother, (void*)stream) == 0;
+  TORCH_CHECK(!mats.empty(), "flat kernel supports 3..8 modes");
+  return by_store(vals, mats[0], [&](auto v, auto s) {
+    using V = TAG_TYPE(v);
+    const int rc = flat_launch<V, TAG_TYPE(s), V>(rowptr, p0, c10::nullopt,
+                                                  idx, mats, vals, out,
+                                                  stream);
+    if (rc > 0) check_rc(rc, "flat MTTKRP");
+    return rc == 0;
+  });
 }
 
 // f32 value stream of an f64 tensor (values all f32-exact, narrowed once by
@@ -761,43 +570,10 @@ static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
                                    std::vector<Tensor> idx,
                                    std::vector<Tensor> mats, Tensor vals32,
                                    Tensor out, int64_t stream) {
-  const int nother = (int)idx.size();
-  TORCH_CHECK(nother >= 2 && nother <= 7, "flat kernel supports 3..8 modes");
-  TORCH_CHECK((int)mats.size() == nother);
-  TORCH_CHECK(rowptr.has_value() != key.has_value(),
-              "pass row pointers or a key stream, not both");
-  TORCH_CHECK(vals32.is_cuda() && vals32.scalar_type() == torch::kFloat32
-              && vals32.is_contiguous(), "vals32 must be contiguous f32");
-  TORCH_CHECK(out.scalar_type() == torch::kFloat64 && out.is_contiguous(),
-              "out must be contiguous f64");
-  const int rank = (int)mats[0].size(1);
-  const int64_t nnz = vals32.numel();
-  const int32_t * ip[8] = {};
-  const double * mp[8] = {};
-  for (int t = 0; t < nother; ++t) {
-    TORCH_CHECK(idx[t].scalar_type() == torch::kInt32
-                && idx[t].numel() == nnz, "idx must be int32 of nnz entries");
-    TORCH_CHECK(mats[t].scalar_type() == torch::kFloat64
-                && mats[t].is_contiguous(), "factors must be contiguous f64");
-    ip[t] = idx[t].data_ptr<int32_t>();
-    mp[t] = mats[t].data_ptr<double>();
-  }
-  if (rowptr.has_value()) {
-    TORCH_CHECK(rowptr->scalar_type() == torch::kInt64
-                && rowptr->is_contiguous() && rowptr->numel() >= 2
-                && rowptr->numel() <= out.size(0) + 1,
-                "rowptr must be contiguous int64 with at most rows + 1 "
-                "entries");
-    return splatt_hip_mttkrp_flat_rp_f64v32(
-               rowptr->data_ptr<int64_t>(), rowptr->numel() - 1, p0, ip, mp,
-               vals32.data_ptr<float>(), nnz, out.data_ptr<double>(), rank,
-               nother, (void*)stream) == 0;
-  }
-  TORCH_CHECK(key->scalar_type() == torch::kInt32 && key->numel() == nnz,
-              "key must be int32 of nnz entries");
-  return splatt_hip_mttkrp_flat_f64v32(
-             key->data_ptr<int32_t>(), ip, mp, vals32.data_ptr<float>(), nnz,
-             out.data_ptr<double>(), rank, nother, (void*)stream) == 0;
+  const int rc = flat_launch<double, double, float>(rowptr, p0, key, idx, mats,
+                                                    vals32, out, stream);
+  if (rc > 0) check_rc(rc, "flat MTTKRP");
+  return rc == 0;
 }
 
 // deterministic flat MTTKRP (csrc/hip/mttkrp_det.hip): plain stores for
@@ -805,300 +581,357 @@ static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
 static void py_gpu_mttkrp_flat_det(Tensor key, std::vector<Tensor> idx,
                                    std::vector<Tensor> mats, Tensor vals,
                                    Tensor out, Tensor side, int64_t stream) {
-  const int nother = (int)idx.size();
+  const size_t nother = idx.size();
   TORCH_CHECK(nother >= 2 && nother <= 4,
               "deterministic kernel supports 3..5 modes");
-  TORCH_CHECK((int)mats.size() == nother);
-  const int rank = (int)mats[0].size(1);
-  const int64_t nnz = vals.numel();
-  const int32_t * ip[8] = {};
-  for (int t = 0; t < nother; ++t) ip[t] = idx[t].data_ptr<int32_t>();
-  int rc;
-  if (vals.scalar_type() == torch::kFloat64) {
-    const double * mp[8] = {};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<double>();
-    rc = splatt_hip_mttkrp_flat_det_f64(key.data_ptr<int32_t>(), ip, mp,
-                                        vals.data_ptr<double>(), nnz,
-                                        out.data_ptr<double>(),
-                                        side.data_ptr<double>(),
-                                        side.numel(), rank, nother,
-                                        (void*)stream);
-  } else {
-    const float * mp[8] = {};
-    for (int t = 0; t < nother; ++t) mp[t] = mats[t].data_ptr<float>();
-    rc = splatt_hip_mttkrp_flat_det_f32(key.data_ptr<int32_t>(), ip, mp,
-                                        vals.data_ptr<float>(), nnz,
-                                        out.data_ptr<float>(),
-                                        side.data_ptr<float>(),
-                                        side.numel(), rank, nother,
-                                        (void*)stream);
+  by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * vp = dev_ptr<V>(vals, "vals");
+    const int64_t nnz = vals.numel();
+    const int rank = rank_of(mats);
+    const int32_t * kp = dev_ptr<int32_t>(key, "key");
+    TORCH_CHECK(key.numel() == nnz, "key must be int32 of nnz entries");
+    auto ip = stream_table(idx, nother, nnz);
+    auto mp = factor_table<V>(mats, nother, rank);
+    const int rc = gpu::mttkrp_flat_det<V>(
+        kp, ip.data(), mp.data(), vp, nnz, out_ptr<V>(out, rank),
+        dev_ptr<V>(side, "side"), side.numel(), rank, (int)nother,
+        (void *)stream);
+    if (rc == -2)
+      check_rc(rc, "deterministic MTTKRP", c10::str(
+          "deterministic workspace too small (", side.numel(), " elems < ",
+          gpu::flat_det_ws(nnz, rank), ")"));
+    check_rc(rc, "deterministic MTTKRP", "deterministic kernel requires rank "
+             "in {4,8,16,32,64} and <= 5 modes");
+  });
+}
+
+// LDS-staged variant: idx[0]/mats[0] is the bucketed level; block
+// descriptors carry (nnz range, bucket row0)
+static void py_gpu_mttkrp_flat5(Tensor key, std::vector<Tensor> idx,
+                                std::vector<Tensor> mats, Tensor vals,
+                                Tensor blk_start, Tensor blk_end,
+                                Tensor blk_row0, int64_t chunk, int64_t dim0,
+                                Tensor out, int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 4, "flat5 supports 3..5 modes");
+  by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * vp = dev_ptr<V>(vals, "vals");
+    const int64_t nnz = vals.numel();
+    const int rank = rank_of(mats);
+    const int32_t * kp = dev_ptr<int32_t>(key, "key");
+    TORCH_CHECK(key.numel() == nnz, "key must be int32 of nnz entries");
+    auto ip = stream_table(idx, nother, nnz);
+    auto mp = factor_table<V>(mats, nother, rank);
+    const StageBlocks blk(blk_start, blk_end, blk_row0);
+    check_rc(gpu::mttkrp_flat5<V>(kp, ip.data(), mp.data(), vp, blk.start,
+                                  blk.end, blk.row0, blk.n, (int32_t)chunk,
+                                  (int32_t)dim0, out_ptr<V>(out, rank), rank,
+                                  (int)nother, (void *)stream), "flat5");
+  });
+}
+
+// packed-stream LDS variant: one int4 word per nonzero
+// (x = output key, y = staged level, z/w = remaining levels)
+static void py_gpu_mttkrp_flat6(Tensor pack, std::vector<Tensor> mats,
+                                Tensor vals, Tensor blk_start,
+                                Tensor blk_end, Tensor blk_row0,
+                                int64_t chunk, int64_t dim0, Tensor out,
+                                int64_t stream) {
+  const size_t nother = mats.size();
+  TORCH_CHECK(nother >= 2 && nother <= 3, "flat6 supports 3..4 modes");
+  by_store(vals, mats[0], [&](auto v, auto s) {
+    using V = TAG_TYPE(v);
+    using S = TAG_TYPE(s);
+    const V * vp = dev_ptr<V>(vals, "vals");
+    const int32_t * pp = pack_ptr(pack, vals.numel());
+    const int rank = rank_of(mats);
+    auto mp = factor_table<S>(mats, nother, rank);
+    const StageBlocks blk(blk_start, blk_end, blk_row0);
+    check_rc(gpu::mttkrp_flat6<V, S>(pp, mp.data(), vp, blk.start, blk.end,
+                                     blk.row0, blk.n, (int32_t)chunk,
+                                     (int32_t)dim0, out_ptr<V>(out, rank),
+                                     rank, (int)nother, (void *)stream),
+             "flat6");
+  });
+}
+
+// LDS-staged bitwise-deterministic MTTKRP over the packed stream:
+// per-bucket privatized outputs + ordered fixup + ascending-bucket fold
+static void py_gpu_mttkrp_det6(Tensor pack, std::vector<Tensor> mats,
+                               Tensor vals, Tensor blk_start,
+                               Tensor blk_end, Tensor blk_row0,
+                               Tensor blk_bucket_p0,
+                               int64_t chunk, int64_t dim0,
+                               int64_t nbuckets, Tensor outb, Tensor side,
+                               Tensor out, int64_t stream) {
+  const size_t nother = mats.size();
+  TORCH_CHECK(nother >= 2 && nother <= 3, "det6 supports 3..4 modes");
+  by_dtype(vals, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * vp = dev_ptr<V>(vals, "vals");
+    const int32_t * pp = pack_ptr(pack, vals.numel());
+    const int rank = rank_of(mats);
+    auto mp = factor_table<V>(mats, nother, rank);
+    const StageBlocks blk(blk_start, blk_end, blk_row0);
+    const int64_t * bp0 = dev_ptr<int64_t>(blk_bucket_p0, "blk_bucket_p0");
+    TORCH_CHECK(blk_bucket_p0.numel() == blk.n,
+                "block descriptor lengths differ");
+    V * op = out_ptr<V>(out, rank);
+    const int64_t nrows_out = out.size(0);
+    V * ob = dev_ptr<V>(outb, "outb");
+    V * sd = dev_ptr<V>(side, "side");
+    // what the launcher zeroes and the kernels then write (launchers.hpp)
+    TORCH_CHECK(rank >= 1 && nbuckets >= 0
+                && outb.numel() >= nbuckets * nrows_out * rank
+                && side.numel() >= blk.n * 4 * (64 / rank) * 2 * rank,
+                "det6 workspace too small");
+    const int rc = gpu::mttkrp_det6<V>(
+        pp, mp.data(), vp, blk.start, blk.end, blk.row0, bp0, blk.n,
+        (int32_t)chunk, (int32_t)dim0, nrows_out, nbuckets, ob, sd, op, rank,
+        (int)nother, (void *)stream);
+    check_rc(rc, "det6",
+             c10::str("det6 supports spec ranks and 3-4 modes, rc=", rc));
+  });
+}
+
+// --------------------------------------------------------- dense ops (HIP)
+
+// A [n, F] of a dense kernel; returns F
+static int dense_rank(const Tensor & A, const char * name) {
+  TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1, name, " must be [n, F]");
+  return (int)A.size(1);
+}
+
+// G (FxF, pre-zeroed) += A^T A for tall-skinny device A
+static void py_gpu_gram(Tensor A, Tensor G, int64_t stream) {
+  by_dtype(A, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * a = dev_ptr<V>(A, "A");
+    const int F = dense_rank(A, "A");
+    TORCH_CHECK(F <= 64 && G.numel() == (int64_t)F * F,
+                "G must be [F, F] with F <= 64");
+    check_rc(gpu::gram<V>(a, A.size(0), F, dev_ptr<V>(G, "G"),
+                          (void *)stream), "gram");
+  });
+}
+
+static void py_gpu_gram_det(Tensor A, Tensor Gpart, Tensor G, int64_t stream) {
+  by_dtype(A, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * a = dev_ptr<V>(A, "A");
+    const int F = dense_rank(A, "A");
+    V * gp = dev_ptr<V>(Gpart, "Gpart");
+    const int64_t nparts = Gpart.numel() / (F * F);
+    TORCH_CHECK(nparts >= 1, "gram_det workspace too small");
+    TORCH_CHECK(G.numel() == (int64_t)F * F, "G must be [F, F]");
+    check_rc(gpu::gram_det<V>(a, A.size(0), F, gp, nparts,
+                              dev_ptr<V>(G, "G"), (void *)stream),
+             "gram_det");
+  });
+}
+
+static void py_gpu_rowsolve(Tensor A, Tensor B, Tensor C, int64_t stream) {
+  by_dtype(A, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * a = dev_ptr<V>(A, "A");
+    const int F = dense_rank(A, "A");
+    const V * b = dev_ptr<V>(B, "B");
+    V * c = dev_ptr<V>(C, "C");
+    TORCH_CHECK(B.numel() == (int64_t)F * F, "B must be [F, F]");
+    TORCH_CHECK(C.numel() == A.numel(), "C must have the shape of A");
+    check_rc(gpu::rowsolve<V>(a, b, c, A.size(0), F, (void *)stream),
+             "rowsolve",
+             c10::str("rowsolve supports F in {4,8,16,32,64}, got ", F));
+  });
+}
+
+static void py_gpu_spd_inverse(Tensor G, Tensor Ginv, int64_t stream) {
+  by_dtype(G, [&](auto tag) {
+    using V = TAG_TYPE(tag);
+    const V * g = dev_ptr<V>(G, "G");
+    TORCH_CHECK(G.dim() == 2 && G.size(0) == G.size(1) && G.size(0) <= 64
+                && Ginv.numel() == G.numel(),
+                "G and Ginv must be [F, F] with F <= 64");
+    check_rc(gpu::spd_inverse<V>(g, dev_ptr<V>(Ginv, "Ginv"), (int)G.size(0),
+                                 (void *)stream), "spd_inverse");
+  });
+}
+
+// column helpers of the C-API device driver (csrc/capi/capi_gpu.cpp)
+static void py_gpu_colacc(Tensor A, int which, Tensor out, int64_t stream) {
+  check_dev(A, torch::kFloat64, "A");
+  check_dev(out, torch::kFloat64, "out");
+  TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+              "A must be [n, F] with 1 <= F <= 64");
+  TORCH_CHECK(out.numel() == A.size(1), "out length != F");
+  TORCH_CHECK(which == 0 || which == 1,
+              "which: 0 = sum of squares, 1 = max |x|");
+  check_rc(gpu::colacc(A.data_ptr<double>(), A.size(0), (int)A.size(1), which,
+                       out.data_ptr<double>(), (void *)stream), "colacc");
+}
+
+static void py_gpu_colscale(Tensor A, Tensor lam, int64_t stream) {
+  check_dev(A, torch::kFloat64, "A");
+  check_dev(lam, torch::kFloat64, "lam");
+  TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+              "A must be [n, F] with 1 <= F <= 64");
+  TORCH_CHECK(lam.numel() == A.size(1), "lam length != F");
+  check_rc(gpu::colscale(A.data_ptr<double>(), A.size(0), (int)A.size(1),
+                         lam.data_ptr<double>(), (void *)stream), "colscale");
+}
+
+static void py_gpu_coldot(Tensor X, Tensor A, Tensor out, int64_t stream) {
+  check_dev(X, torch::kFloat64, "X");
+  check_dev(A, torch::kFloat64, "A");
+  check_dev(out, torch::kFloat64, "out");
+  TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
+              "A must be [n, F] with 1 <= F <= 64");
+  TORCH_CHECK(X.dim() == 2 && X.size(0) == A.size(0)
+              && X.size(1) == A.size(1), "X and A shapes differ");
+  TORCH_CHECK(out.numel() == A.size(1), "out length != F");
+  check_rc(gpu::coldot(X.data_ptr<double>(), A.data_ptr<double>(), A.size(0),
+                       (int)A.size(1), out.data_ptr<double>(),
+                       (void *)stream), "coldot");
+}
+
+// --------------------------- segment batches (completion, TTMc; f64 only)
+
+// One batch of a root-sorted stream cut into segments: segments
+// [seg0, seg0+nseg) accumulate, then multi-segment rows [m0, m0+nm) are
+// folded from the workspace, where slots slot0..slot0+nslots-1 (slot_elems
+// doubles each) live during this batch.
+struct SegBatch {
+  const int64_t * seg_start;
+  const int32_t * seg_len, * seg_row, * seg_slot, * mrow;
+  const int64_t * mslot;
+  double * ws;
+  SegBatch(const Tensor & seg_start_, const Tensor & seg_len_,
+           const Tensor & seg_row_, const Tensor & seg_slot_, int64_t seg0,
+           int64_t nseg, const Tensor & mrow_, const Tensor & mslot_,
+           int64_t m0, int64_t nm, int64_t slot0, int64_t nslots,
+           const Tensor & ws_, int64_t slot_elems, const char * ws_msg)
+      : seg_start(dev_ptr<int64_t>(seg_start_, "seg_start")),
+        seg_len(dev_ptr<int32_t>(seg_len_, "seg_len")),
+        seg_row(dev_ptr<int32_t>(seg_row_, "seg_row")),
+        seg_slot(dev_ptr<int32_t>(seg_slot_, "seg_slot")),
+        mrow(dev_ptr<int32_t>(mrow_, "mrow")),
+        mslot(dev_ptr<int64_t>(mslot_, "mslot")),
+        ws(dev_ptr<double>(ws_, "ws")) {
+    TORCH_CHECK(seg_len_.numel() == seg_start_.numel()
+                && seg_row_.numel() == seg_start_.numel()
+                && seg_slot_.numel() == seg_start_.numel());
+    TORCH_CHECK(seg0 >= 0 && nseg >= 0 && seg0 + nseg <= seg_start_.numel(),
+                "segment range out of bounds");
+    TORCH_CHECK(m0 >= 0 && nm >= 0 && m0 + nm <= mrow_.numel()
+                && mslot_.numel() == mrow_.numel() + 1,
+                "multi-segment row range out of bounds");
+    TORCH_CHECK(nslots >= 0 && slot0 >= 0
+                && ws_.numel() >= nslots * slot_elems, ws_msg);
   }
-  TORCH_CHECK(rc != -1, "deterministic kernel requires rank in "
-                        "{4,8,16,32,64} and <= 5 modes");
-  TORCH_CHECK(rc == 0, "deterministic workspace too small (", side.numel(),
-              " elems < ", splatt_hip_flat_det_ws(nnz, rank), ")");
-}
-
-// thin wrappers: Python passes contiguous CUDA tensors + stream handle
-template <typename V>
-static void gpu_mttkrp3_t(int which, Tensor fptr0, py::object fids0, Tensor fptr1,
-                          Tensor fids1, Tensor fids2, Tensor vals,
-                          Tensor Ma, Tensor Mb, Tensor out, int64_t stream) {
-  const int64_t nslices = fptr0.numel() - 1;
-  const int64_t nfibs = fptr1.numel() - 1;
-  const int64_t nnz = vals.numel();
-  const int rank = (int)Ma.size(1);
-  const int32_t * f0 = fids0.is_none() ? nullptr
-                       : fids0.cast<Tensor>().data_ptr<int32_t>();
-  const bool f64 = std::is_same<V, double>::value;
-  auto fp0 = fptr0.data_ptr<int64_t>();
-  auto fp1 = fptr1.data_ptr<int64_t>();
-  auto fi1 = fids1.data_ptr<int32_t>();
-  auto fi2 = fids2.data_ptr<int32_t>();
-  auto vp = vals.data_ptr<V>();
-  auto a = Ma.data_ptr<V>();
-  auto b = Mb.data_ptr<V>();
-  auto o = out.data_ptr<V>();
-  void * s = (void*)stream;
-  if (f64) {
-    auto vd = (const double*)vp; auto ad = (const double*)a;
-    auto bd = (const double*)b; auto od = (double*)o;
-    if (which == 0) splatt_hip_mttkrp_root3_f64(fp0, f0, fp1, fi1, fi2, vd, nslices, nfibs, nnz, ad, bd, od, rank, s);
-    else if (which == 1) splatt_hip_mttkrp_intl3_f64(fp0, f0, fp1, fi1, fi2, vd, nslices, nfibs, nnz, ad, bd, od, rank, s);
-    else splatt_hip_mttkrp_leaf3_f64(fp0, f0, fp1, fi1, fi2, vd, nslices, nfibs, nnz, ad, bd, od, rank, s);
-  } else {
-    auto vf = (const float*)vp; auto af = (const float*)a;
-    auto bf = (const float*)b; auto of = (float*)o;
-    if (which == 0) splatt_hip_mttkrp_root3_f32(fp0, f0, fp1, fi1, fi2, vf, nslices, nfibs, nnz, af, bf, of, rank, s);
-    else if (which == 1) splatt_hip_mttkrp_intl3_f32(fp0, f0, fp1, fi1, fi2, vf, nslices, nfibs, nnz, af, bf, of, rank, s);
-    else splatt_hip_mttkrp_leaf3_f32(fp0, f0, fp1, fi1, fi2, vf, nslices, nfibs, nnz, af, bf, of, rank, s);
-  }
-}
-
-static void py_gpu_mttkrp3(int which, Tensor fptr0, py::object fids0, Tensor fptr1,
-                           Tensor fids1, Tensor fids2, Tensor vals,
-                           Tensor Ma, Tensor Mb, Tensor out, int64_t stream) {
-  if (vals.scalar_type() == torch::kFloat32)
-    gpu_mttkrp3_t<float>(which, fptr0, fids0, fptr1, fids1, fids2, vals, Ma, Mb, out, stream);
-  else
-    gpu_mttkrp3_t<double>(which, fptr0, fids0, fptr1, fids1, fids2, vals, Ma, Mb, out, stream);
-}
-
-// ------------------------------------------- tensor completion (f64 only)
-extern "C" {
-// csrc/hip/complete_als.hip; nonzero return = hipError_t of the launch
-int64_t splatt_hip_complete_slot_elems(int);
-const char * splatt_hip_complete_errstr(int);
-int splatt_hip_complete_segments_f64(
-    const int32_t* const*, const double* const*, int, const double*,
-    const int64_t*, const int32_t*, const int32_t*, const int32_t*, int64_t,
-    int64_t, int64_t, int, double, double*, double*, void*);
-int splatt_hip_complete_reduce_f64(
-    const double*, const int32_t*, const int64_t*, int64_t, int64_t, int64_t,
-    int, double, double*, void*);
-int splatt_hip_kruskal_predict_f64(
-    const int64_t* const*, const double* const*, int, const double*, int64_t,
-    int, double*, void*);
-}
-
-static void check_dev(const Tensor & t, torch::ScalarType ty,
-                      const char * name) {
-  TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
-  TORCH_CHECK(t.scalar_type() == ty, name, " has dtype ", t.scalar_type(),
-              ", expected ", ty);
-  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-}
+};
 
 // One batch of the row-wise completion update for a root-sorted stream:
-// segments [seg0, seg0+nseg) accumulate (and solve single-segment rows),
-// then multi-segment rows [m0, m0+nm) are folded from `ws` and solved.
-// Slots slot0..slot0+nslots-1 live in `ws` during this batch.
+// segments accumulate (and solve single-segment rows), then multi-segment
+// rows are folded from `ws` and solved.
 static void py_gpu_complete_update(
     std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
     Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
     int64_t seg0, int64_t nseg, Tensor mrow, Tensor mslot, int64_t m0,
     int64_t nm, int64_t slot0, int64_t nslots, double reg, Tensor ws,
     Tensor out, int64_t stream) {
-  const int nother = (int)idx.size();
+  const size_t nother = idx.size();
   TORCH_CHECK(nother >= 2 && nother <= 7, "completion supports 3..8 modes");
-  TORCH_CHECK((int)mats.size() == nother);
   TORCH_CHECK(reg > 0.0, "reg must be > 0");
-  check_dev(vals, torch::kFloat64, "vals");
-  check_dev(out, torch::kFloat64, "out");
-  check_dev(ws, torch::kFloat64, "ws");
-  check_dev(seg_start, torch::kInt64, "seg_start");
-  check_dev(seg_len, torch::kInt32, "seg_len");
-  check_dev(seg_row, torch::kInt32, "seg_row");
-  check_dev(seg_slot, torch::kInt32, "seg_slot");
-  check_dev(mrow, torch::kInt32, "mrow");
-  check_dev(mslot, torch::kInt64, "mslot");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  double * op = dev_ptr<double>(out, "out");
   TORCH_CHECK(out.dim() == 2, "out must be [rows, rank]");
   const int F = (int)out.size(1);
   TORCH_CHECK(F >= 1 && F <= 64, "completion supports rank 1..64, got ", F);
-  const int64_t nnz = vals.numel();
-  const int32_t * ip[8] = {};
-  const double * mp[8] = {};
-  for (int t = 0; t < nother; ++t) {
-    check_dev(idx[t], torch::kInt32, "idx");
-    check_dev(mats[t], torch::kFloat64, "factor");
-    TORCH_CHECK(idx[t].numel() == nnz, "index stream length != nnz");
-    TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) == F,
-                "factor rank mismatch");
-    ip[t] = idx[t].data_ptr<int32_t>();
-    mp[t] = mats[t].data_ptr<double>();
-  }
-  TORCH_CHECK(seg_len.numel() == seg_start.numel()
-              && seg_row.numel() == seg_start.numel()
-              && seg_slot.numel() == seg_start.numel());
-  TORCH_CHECK(seg0 >= 0 && nseg >= 0 && seg0 + nseg <= seg_start.numel(),
-              "segment range out of bounds");
-  TORCH_CHECK(m0 >= 0 && nm >= 0 && m0 + nm <= mrow.numel()
-              && mslot.numel() == mrow.numel() + 1,
-              "multi-segment row range out of bounds");
-  TORCH_CHECK(nslots >= 0 && slot0 >= 0
-              && ws.numel() >= nslots * splatt_hip_complete_slot_elems(F),
-              "completion workspace too small");
-  int rc = splatt_hip_complete_segments_f64(
-      ip, mp, nother, vals.data_ptr<double>(), seg_start.data_ptr<int64_t>(),
-      seg_len.data_ptr<int32_t>(), seg_row.data_ptr<int32_t>(),
-      seg_slot.data_ptr<int32_t>(), seg0, nseg, slot0, F, reg,
-      ws.data_ptr<double>(), out.data_ptr<double>(), (void*)stream);
-  TORCH_CHECK(rc == 0, "completion segment kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
-  rc = splatt_hip_complete_reduce_f64(
-      ws.data_ptr<double>(), mrow.data_ptr<int32_t>(),
-      mslot.data_ptr<int64_t>(), m0, nm, slot0, F, reg,
-      out.data_ptr<double>(), (void*)stream);
-  TORCH_CHECK(rc == 0, "completion reduce kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
+  auto ip = stream_table(idx, nother, vals.numel());
+  auto mp = factor_table<double>(mats, nother, F);
+  const SegBatch b(seg_start, seg_len, seg_row, seg_slot, seg0, nseg, mrow,
+                   mslot, m0, nm, slot0, nslots, ws,
+                   gpu::complete_slot_elems(F),
+                   "completion workspace too small");
+  check_rc(gpu::complete_segments(
+               ip.data(), mp.data(), (int)nother, vp, b.seg_start, b.seg_len,
+               b.seg_row, b.seg_slot, seg0, nseg, slot0, F, reg, b.ws, op,
+               (void *)stream), "completion segment");
+  check_rc(gpu::complete_reduce(b.ws, b.mrow, b.mslot, m0, nm, slot0, F, reg,
+                                op, (void *)stream), "completion reduce");
 }
 
 // out[p] = sum_f lam_f prod_t mats[t][inds[t,p], f]; inds is [nmodes, n]
 static void py_gpu_kruskal_predict(Tensor inds, std::vector<Tensor> mats,
                                    py::object lam, Tensor out,
                                    int64_t stream) {
-  check_dev(inds, torch::kInt64, "inds");
-  check_dev(out, torch::kFloat64, "out");
+  const int64_t * base = dev_ptr<int64_t>(inds, "inds");
+  double * op = dev_ptr<double>(out, "out");
   TORCH_CHECK(inds.dim() == 2, "inds must be [nmodes, n]");
-  const int nm = (int)inds.size(0);
+  const size_t nm = (size_t)inds.size(0);
   const int64_t n = inds.size(1);
-  TORCH_CHECK(nm >= 1 && nm <= 8 && (int)mats.size() == nm,
+  TORCH_CHECK(nm >= 1 && nm <= 8 && mats.size() == nm,
               "need one factor per mode (1..8 modes)");
   TORCH_CHECK(out.numel() == n, "out length != number of coordinates");
-  const int F = (int)mats[0].size(1);
+  const int F = rank_of(mats);
+  auto mp = factor_table<double>(mats, nm, F);
   const int64_t * ip[8] = {};
-  const double * mp[8] = {};
-  for (int t = 0; t < nm; ++t) {
-    check_dev(mats[t], torch::kFloat64, "factor");
-    TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) == F,
-                "factor rank mismatch");
-    ip[t] = inds.data_ptr<int64_t>() + (int64_t)t * n;
-    mp[t] = mats[t].data_ptr<double>();
-  }
+  for (size_t t = 0; t < nm; ++t) ip[t] = base + (int64_t)t * n;
   const double * lp = nullptr;
   Tensor lt;
   if (!lam.is_none()) {
     lt = lam.cast<Tensor>();
-    check_dev(lt, torch::kFloat64, "lam");
+    lp = dev_ptr<double>(lt, "lam");
     TORCH_CHECK(lt.numel() == F, "lam length != rank");
-    lp = lt.data_ptr<double>();
   }
-  const int rc = splatt_hip_kruskal_predict_f64(
-      ip, mp, nm, lp, n, F, out.data_ptr<double>(), (void*)stream);
-  TORCH_CHECK(rc == 0, "kruskal_predict kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
+  check_rc(gpu::kruskal_predict(ip, mp.data(), (int)nm, lp, n, F, op,
+                                (void *)stream), "kruskal_predict");
 }
 
-// ------------------------------------------------ Tucker / TTMc (f64 only)
-extern "C" {
-// csrc/hip/ttmc.hip; nonzero return = hipError_t of the launch
-int splatt_hip_ttmc_max_cols();
-int splatt_hip_ttmc_segments_f64(
-    const int32_t* const*, const double* const*, const int*, int,
-    const double*, const int64_t*, const int32_t*, const int32_t*,
-    const int32_t*, int64_t, int64_t, int64_t, double*, double*, void*);
-int splatt_hip_ttmc_reduce_f64(
-    const double*, const int32_t*, const int64_t*, int64_t, int64_t, int64_t,
-    int, double*, void*);
-}
-
-// One batch of the TTMc of a root-sorted stream: segments [seg0, seg0+nseg)
-// accumulate (single-segment rows go straight to `out`), then multi-segment
-// rows [m0, m0+nm) are folded from `ws`. idx/mats are the non-root levels
-// in level order; `out` is [rows, prod of their ranks] in that order. Slots
-// slot0..slot0+nslots-1 (one output row each) live in `ws` during the batch.
+// One batch of the TTMc of a root-sorted stream: segments accumulate
+// (single-segment rows go straight to `out`), then multi-segment rows are
+// folded from `ws`. idx/mats are the non-root levels in level order; `out`
+// is [rows, prod of their ranks] in that order; a slot is one output row.
 static void py_gpu_ttmc(
     std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
     Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
     int64_t seg0, int64_t nseg, Tensor mrow, Tensor mslot, int64_t m0,
     int64_t nm, int64_t slot0, int64_t nslots, Tensor ws, Tensor out,
     int64_t stream) {
-  const int nother = (int)idx.size();
+  const size_t nother = idx.size();
   TORCH_CHECK(nother >= 2 && nother <= 7, "ttmc supports 3..8 modes");
-  TORCH_CHECK((int)mats.size() == nother);
-  check_dev(vals, torch::kFloat64, "vals");
-  check_dev(out, torch::kFloat64, "out");
-  check_dev(ws, torch::kFloat64, "ws");
-  check_dev(seg_start, torch::kInt64, "seg_start");
-  check_dev(seg_len, torch::kInt32, "seg_len");
-  check_dev(seg_row, torch::kInt32, "seg_row");
-  check_dev(seg_slot, torch::kInt32, "seg_slot");
-  check_dev(mrow, torch::kInt32, "mrow");
-  check_dev(mslot, torch::kInt64, "mslot");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  double * op = dev_ptr<double>(out, "out");
   TORCH_CHECK(out.dim() == 2, "out must be [rows, columns]");
-  const int64_t nnz = vals.numel();
-  const int32_t * ip[8] = {};
-  const double * mp[8] = {};
+  auto ip = stream_table(idx, nother, vals.numel());
+  auto mp = ptr_table<double>(mats, nother, "factor");
   int ranks[8] = {};
   int64_t P = 1;
-  for (int t = 0; t < nother; ++t) {
-    check_dev(idx[t], torch::kInt32, "idx");
-    check_dev(mats[t], torch::kFloat64, "factor");
-    TORCH_CHECK(idx[t].numel() == nnz, "index stream length != nnz");
+  for (size_t t = 0; t < nother; ++t) {
     TORCH_CHECK(mats[t].dim() == 2 && mats[t].size(1) >= 1
                 && mats[t].size(1) <= 32,
                 "ttmc supports rank 1..32 per mode, got ", mats[t].size(1));
-    ip[t] = idx[t].data_ptr<int32_t>();
-    mp[t] = mats[t].data_ptr<double>();
     ranks[t] = (int)mats[t].size(1);
     P *= ranks[t];
   }
-  TORCH_CHECK(P <= splatt_hip_ttmc_max_cols(), "ttmc kernel supports at most ",
-              splatt_hip_ttmc_max_cols(), " output columns, got ", P);
+  TORCH_CHECK(P <= gpu::ttmc_max_cols(), "ttmc kernel supports at most ",
+              gpu::ttmc_max_cols(), " output columns, got ", P);
   TORCH_CHECK(out.size(1) == P, "out has ", out.size(1), " columns, expected ",
               P);
-  TORCH_CHECK(seg_len.numel() == seg_start.numel()
-              && seg_row.numel() == seg_start.numel()
-              && seg_slot.numel() == seg_start.numel());
-  TORCH_CHECK(seg0 >= 0 && nseg >= 0 && seg0 + nseg <= seg_start.numel(),
-              "segment range out of bounds");
-  TORCH_CHECK(m0 >= 0 && nm >= 0 && m0 + nm <= mrow.numel()
-              && mslot.numel() == mrow.numel() + 1,
-              "multi-segment row range out of bounds");
-  TORCH_CHECK(nslots >= 0 && slot0 >= 0 && ws.numel() >= nslots * P,
-              "ttmc workspace too small");
-  int rc = splatt_hip_ttmc_segments_f64(
-      ip, mp, ranks, nother, vals.data_ptr<double>(),
-      seg_start.data_ptr<int64_t>(), seg_len.data_ptr<int32_t>(),
-      seg_row.data_ptr<int32_t>(), seg_slot.data_ptr<int32_t>(), seg0, nseg,
-      slot0, ws.data_ptr<double>(), out.data_ptr<double>(), (void*)stream);
-  TORCH_CHECK(rc == 0, "ttmc segment kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
-  rc = splatt_hip_ttmc_reduce_f64(
-      ws.data_ptr<double>(), mrow.data_ptr<int32_t>(),
-      mslot.data_ptr<int64_t>(), m0, nm, slot0, (int)P,
-      out.data_ptr<double>(), (void*)stream);
-  TORCH_CHECK(rc == 0, "ttmc reduce kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
+  const SegBatch b(seg_start, seg_len, seg_row, seg_slot, seg0, nseg, mrow,
+                   mslot, m0, nm, slot0, nslots, ws, P,
+                   "ttmc workspace too small");
+  check_rc(gpu::ttmc_segments(
+               ip.data(), mp.data(), ranks, (int)nother, vp, b.seg_start,
+               b.seg_len, b.seg_row, b.seg_slot, seg0, nseg, slot0, b.ws, op,
+               (void *)stream), "ttmc segment");
+  check_rc(gpu::ttmc_reduce(b.ws, b.mrow, b.mslot, m0, nm, slot0, (int)P, op,
+                            (void *)stream), "ttmc reduce");
 }
 
 // ------------------------------------- constrained CPD / AO-ADMM (f64 only)
-extern "C" {
-// csrc/hip/admm.hip; nonzero return = hipError_t of the launch
-int splatt_hip_admm_update_f64(
-    const double*, const double*, const double*, double*, double*, int32_t*,
-    int64_t, int, int, double, double, double, double, int, int, void*);
-}
 
 // The fused block-ADMM update of one factor: H and U are updated in place,
 // iters receives one inner-iteration count per block of 64 rows.
@@ -1130,24 +963,22 @@ static void py_gpu_admm_update(Tensor K, Tensor Ginv, Tensor rho, Tensor H,
   TORCH_CHECK(variant == 0 || variant == 1
               || (variant == 2 && (F == 16 || F == 32 || F == 64)),
               "the MFMA variant exists for ranks 16, 32 and 64 only");
-  const int rc = splatt_hip_admm_update_f64(
-      K.data_ptr<double>(), Ginv.data_ptr<double>(), rho.data_ptr<double>(),
-      H.data_ptr<double>(), U.data_ptr<double>(), iters.data_ptr<int32_t>(),
-      n, F, (int)kind, w, lo, hi, inner_tol, (int)max_inner, (int)variant,
-      (void*)stream);
-  TORCH_CHECK(rc == 0, "admm_update kernel launch failed: ",
-              splatt_hip_complete_errstr(rc));
+  check_rc(gpu::admm_update(
+               K.data_ptr<double>(), Ginv.data_ptr<double>(),
+               rho.data_ptr<double>(), H.data_ptr<double>(),
+               U.data_ptr<double>(), iters.data_ptr<int32_t>(), n, F,
+               (int)kind, w, lo, hi, inner_tol, (int)max_inner, (int)variant,
+               (void *)stream), "admm_update");
 }
 
 // ------------------------------------------ fused dense ALS tail (f64 only)
-extern "C" {
-// csrc/hip/dense_kernels.hip, csrc/hip/als_tail.hip; positive return =
-// hipError_t of the launch, negative = the arguments do not qualify
-int splatt_hip_als_prep_f64(const double* const*, int, double, double*, int,
-                            double*, double*, double*, void*);
-int splatt_hip_als_tail_f64(const double*, const double*, int64_t, int,
-                            double*, double*, double*, double*, void*);
-int64_t splatt_hip_als_tail_cap_rows();
+
+// `inner` of the tail: [rank] when given
+static double * inner_ptr(const c10::optional<Tensor> & inner, int F) {
+  if (!inner.has_value()) return nullptr;
+  double * p = dev_ptr<double>(*inner, "inner");
+  TORCH_CHECK(inner->numel() == F, "inner must be [rank]");
+  return p;
 }
 
 // One launch in front of the tail: Ginv = inverse of the Hadamard product
@@ -1166,26 +997,18 @@ static void py_gpu_als_prep(std::vector<Tensor> grams, double reg,
   TORCH_CHECK(grams.size() <= 8, "at most 8 Gram matrices");
   TORCH_CHECK(gram.numel() == (int64_t)F * F && lam.numel() == F,
               "gram must be [rank, rank] and lam [rank]");
-  const double * gp[8] = {};
-  for (size_t o = 0; o < grams.size(); ++o) {
-    check_dev(grams[o], torch::kFloat64, "grams");
-    TORCH_CHECK(grams[o].numel() == (int64_t)F * F,
+  auto gp = ptr_table<double>(grams, grams.size(), "grams");
+  for (auto & g : grams) {
+    TORCH_CHECK(g.numel() == (int64_t)F * F,
                 "every Gram must be [rank, rank]");
-    TORCH_CHECK(grams[o].data_ptr() != gram.data_ptr(),
+    TORCH_CHECK(g.data_ptr() != gram.data_ptr(),
                 "the Gram being reset cannot be an input");
-    gp[o] = grams[o].data_ptr<double>();
   }
-  double * ip = nullptr;
-  if (inner.has_value()) {
-    check_dev(*inner, torch::kFloat64, "inner");
-    TORCH_CHECK(inner->numel() == F, "inner must be [rank]");
-    ip = inner->data_ptr<double>();
-  }
-  const int rc = splatt_hip_als_prep_f64(
-      gp, (int)grams.size(), reg, Ginv.data_ptr<double>(), F,
-      gram.data_ptr<double>(), lam.data_ptr<double>(), ip, (void*)stream);
-  TORCH_CHECK(rc == 0, "als_prep kernel launch failed: ",
-              rc > 0 ? splatt_hip_complete_errstr(rc) : "bad arguments");
+  check_rc(gpu::als_prep(gp.data(), (int)grams.size(), reg,
+                         Ginv.data_ptr<double>(), F, gram.data_ptr<double>(),
+                         lam.data_ptr<double>(), inner_ptr(inner, F),
+                         (void *)stream),
+           "als_prep", "als_prep kernel launch failed: bad arguments");
 }
 
 // The two passes of the tail. lam, gram and inner accumulate: they must
@@ -1207,19 +1030,12 @@ static void py_gpu_als_tail(Tensor K, Tensor Ginv, Tensor A, Tensor lam,
   TORCH_CHECK(Ginv.numel() == (int64_t)F * F && gram.numel() == (int64_t)F * F
               && lam.numel() == F, "Ginv/gram must be [rank, rank], lam [rank]");
   TORCH_CHECK(K.data_ptr() != A.data_ptr(), "K and A must not alias");
-  double * ip = nullptr;
-  if (inner.has_value()) {
-    check_dev(*inner, torch::kFloat64, "inner");
-    TORCH_CHECK(inner->numel() == F, "inner must be [rank]");
-    ip = inner->data_ptr<double>();
-  }
-  const int rc = splatt_hip_als_tail_f64(
-      K.data_ptr<double>(), Ginv.data_ptr<double>(), n, F,
-      A.data_ptr<double>(), lam.data_ptr<double>(), gram.data_ptr<double>(),
-      ip, (void*)stream);
-  TORCH_CHECK(rc == 0, "als_tail kernel launch failed: ",
-              rc > 0 ? splatt_hip_complete_errstr(rc)
-                     : "rank or alignment does not qualify");
+  check_rc(gpu::als_tail(K.data_ptr<double>(), Ginv.data_ptr<double>(), n, F,
+                         A.data_ptr<double>(), lam.data_ptr<double>(),
+                         gram.data_ptr<double>(), inner_ptr(inner, F),
+                         (void *)stream),
+           "als_tail",
+           "als_tail kernel launch failed: rank or alignment does not qualify");
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1227,17 +1043,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Hadamard of Grams + SPD inverse + reset of the tail accumulators");
   m.def("gpu_als_tail", &py_gpu_als_tail,
         "fused ALS tail: A = (K Ginv)/lam, lam, gram += A^T A, inner");
-  m.def("als_tail_cap_rows", &splatt_hip_als_tail_cap_rows,
+  m.def("als_tail_cap_rows", &gpu::als_tail_cap_rows,
         "row count at which the fused tail's grid reaches its cap");
   m.def("gpu_admm_update", &py_gpu_admm_update,
         "fused block-ADMM factor update (in place on H, U)");
   m.def("gpu_ttmc", &py_gpu_ttmc,
         "TTMc of a root-sorted stream: one batch of segments + row folds");
-  m.def("ttmc_max_cols", &splatt_hip_ttmc_max_cols,
+  m.def("ttmc_max_cols", &gpu::ttmc_max_cols,
         "widest TTMc output row the HIP kernel supports");
   m.def("gpu_complete_update", &py_gpu_complete_update,
         "row-wise completion update: one batch of segments + row solves");
-  m.def("complete_slot_elems", &splatt_hip_complete_slot_elems,
+  m.def("complete_slot_elems", &gpu::complete_slot_elems,
         "workspace doubles per segment slot at a rank");
   m.def("gpu_kruskal_predict", &py_gpu_kruskal_predict,
         "Kruskal model values at COO coordinates");
@@ -1262,81 +1078,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "row pointers or key stream; false = declined, use the f64 stream");
   m.def("gpu_mttkrp_flat_det", &py_gpu_mttkrp_flat_det,
         "bitwise-deterministic flat MTTKRP (depth-0 streams, spec ranks)");
-  m.def("flat_det_ws_elems", &splatt_hip_flat_det_ws,
+  m.def("flat_det_ws_elems", &gpu::flat_det_ws,
         "workspace elements required by gpu_mttkrp_flat_det");
   m.def("gpu_gram", &py_gpu_gram, "G += A^T A (tall-skinny, F<=64)");
-  // column helpers of the C-API device driver (csrc/capi/capi_gpu.cpp)
-  m.def("gpu_colacc", [](Tensor A, int which, Tensor out, int64_t stream) {
-    check_dev(A, torch::kFloat64, "A");
-    check_dev(out, torch::kFloat64, "out");
-    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
-                "A must be [n, F] with 1 <= F <= 64");
-    TORCH_CHECK(out.numel() == A.size(1), "out length != F");
-    TORCH_CHECK(which == 0 || which == 1,
-                "which: 0 = sum of squares, 1 = max |x|");
-    splatt_hip_colacc_f64(A.data_ptr<double>(), A.size(0), (int)A.size(1),
-                          which, out.data_ptr<double>(), (void*)stream);
-  }, "out[f] (pre-zeroed) += sum_i A[i,f]^2 (which=0), or "
-     "out[f] = max(out[f], max_i |A[i,f]|) (which=1)");
-  m.def("gpu_colscale", [](Tensor A, Tensor lam, int64_t stream) {
-    check_dev(A, torch::kFloat64, "A");
-    check_dev(lam, torch::kFloat64, "lam");
-    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
-                "A must be [n, F] with 1 <= F <= 64");
-    TORCH_CHECK(lam.numel() == A.size(1), "lam length != F");
-    splatt_hip_colscale_f64(A.data_ptr<double>(), A.size(0), (int)A.size(1),
-                            lam.data_ptr<double>(), (void*)stream);
-  }, "A[i,f] /= lam[f] in place");
-  m.def("gpu_coldot", [](Tensor X, Tensor A, Tensor out, int64_t stream) {
-    check_dev(X, torch::kFloat64, "X");
-    check_dev(A, torch::kFloat64, "A");
-    check_dev(out, torch::kFloat64, "out");
-    TORCH_CHECK(A.dim() == 2 && A.size(1) >= 1 && A.size(1) <= 64,
-                "A must be [n, F] with 1 <= F <= 64");
-    TORCH_CHECK(X.dim() == 2 && X.size(0) == A.size(0)
-                && X.size(1) == A.size(1), "X and A shapes differ");
-    TORCH_CHECK(out.numel() == A.size(1), "out length != F");
-    splatt_hip_coldot_f64(X.data_ptr<double>(), A.data_ptr<double>(),
-                          A.size(0), (int)A.size(1),
-                          out.data_ptr<double>(), (void*)stream);
-  }, "out[f] (pre-zeroed) += sum_i X[i,f] * A[i,f]");
-  m.def("gpu_gram_det", [](Tensor A, Tensor Gpart, Tensor G,
-                           int64_t stream) {
-    const int64_t n = A.size(0);
-    const int F = (int)A.size(1);
-    const int64_t nparts = Gpart.numel() / (F * F);
-    TORCH_CHECK(nparts >= 1, "gram_det workspace too small");
-    if (A.scalar_type() == torch::kFloat64)
-      splatt_hip_gram_det_f64(A.data_ptr<double>(), n, F,
-                              Gpart.data_ptr<double>(), nparts,
-                              G.data_ptr<double>(), (void*)stream);
-    else
-      splatt_hip_gram_det_f32(A.data_ptr<float>(), n, F,
-                              Gpart.data_ptr<float>(), nparts,
-                              G.data_ptr<float>(), (void*)stream);
-  }, "G = A^T A, per-block partials folded in fixed order "
-     "(bitwise-deterministic)");
-  m.def("gpu_rowsolve", [](Tensor A, Tensor B, Tensor C, int64_t stream) {
-    const int64_t n = A.size(0);
-    const int F = (int)A.size(1);
-    int rc;
-    if (A.scalar_type() == torch::kFloat64)
-      rc = splatt_hip_rowsolve_f64(A.data_ptr<double>(), B.data_ptr<double>(),
-                                   C.data_ptr<double>(), n, F, (void*)stream);
-    else
-      rc = splatt_hip_rowsolve_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                                   C.data_ptr<float>(), n, F, (void*)stream);
-    TORCH_CHECK(rc == 0, "rowsolve supports F in {4,8,16,32,64}, got ", F);
-  }, "C = A @ B (B is FxF, staged in LDS; bitwise-deterministic)");
-  m.def("gpu_spd_inverse", [](Tensor G, Tensor Ginv, int64_t stream) {
-    const int F = (int)G.size(0);
-    if (G.scalar_type() == torch::kFloat64)
-      splatt_hip_spd_inverse_f64(G.data_ptr<double>(), Ginv.data_ptr<double>(),
-                                 F, (void*)stream);
-    else
-      splatt_hip_spd_inverse_f32(G.data_ptr<float>(), Ginv.data_ptr<float>(),
-                                 F, (void*)stream);
-  }, "Ginv = G^-1 for SPD FxF (F<=64), one-workgroup Cholesky");
+  m.def("gpu_colacc", &py_gpu_colacc,
+        "out[f] (pre-zeroed) += sum_i A[i,f]^2 (which=0), or "
+        "out[f] = max(out[f], max_i |A[i,f]|) (which=1)");
+  m.def("gpu_colscale", &py_gpu_colscale, "A[i,f] /= lam[f] in place");
+  m.def("gpu_coldot", &py_gpu_coldot,
+        "out[f] (pre-zeroed) += sum_i X[i,f] * A[i,f]");
+  m.def("gpu_gram_det", &py_gpu_gram_det,
+        "G = A^T A, per-block partials folded in fixed order "
+        "(bitwise-deterministic)");
+  m.def("gpu_rowsolve", &py_gpu_rowsolve,
+        "C = A @ B (B is FxF, staged in LDS; bitwise-deterministic)");
+  m.def("gpu_spd_inverse", &py_gpu_spd_inverse,
+        "Ginv = G^-1 for SPD FxF (F<=64), one-workgroup Cholesky");
   m.def("gpu_mttkrp_flat5", &py_gpu_mttkrp_flat5,
         "LDS-staged flat MTTKRP (bucketed builds, root output)");
   m.def("gpu_mttkrp_flat6", &py_gpu_mttkrp_flat6,
@@ -1348,5 +1105,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto parts = sp::partition_weighted(w.data(), (int64_t)w.size(), nparts, &bn);
     return py::make_tuple(parts, bn);
   }, "optimal chains-on-chains partition (boundaries, bottleneck)");
-  m.def("hip_arch", []() { return splatt_hip_kernels_arch(); });
+  m.def("hip_arch", &gpu::kernels_arch);
 }

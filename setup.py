@@ -22,6 +22,8 @@ HIPCC = str(ROCM / "bin" / "hipcc")
 ARCH = os.environ.get("SPLATT_GPU_ARCH", "gfx950")
 
 HIP_SOURCES = sorted((ROOT / "csrc" / "hip").glob("*.hip"))
+# the launcher declarations both sides of the boundary include
+LAUNCHERS_HPP = ROOT / "csrc" / "hip" / "launchers.hpp"
 CORE_SOURCES = sorted((ROOT / "csrc" / "core").glob("*.cpp"))
 
 
@@ -30,7 +32,8 @@ def build_hip_objects():
     objdir.mkdir(parents=True, exist_ok=True)
     objs = []
     rebuilt = False
-    # headers shared between kernel files (mfma_acc.hpp, store_types.hpp)
+    # headers shared between kernel files (device_common.hpp, launchers.hpp,
+    # mfma_acc.hpp, store_types.hpp)
     hdr_mtime = max((h.stat().st_mtime
                      for h in (ROOT / "csrc" / "hip").glob("*.hpp")),
                     default=0.0)
@@ -67,7 +70,8 @@ def build_native_lib(hip_objs):
     gpu_src = ROOT / "csrc/capi/capi_gpu.cpp"
     newest = max(Path(s).stat().st_mtime
                  for s in srcs + hip_objs
-                 + [str(gpu_src), str(ROOT / "csrc/capi/splatt.h"),
+                 + [str(gpu_src), str(LAUNCHERS_HPP),
+                    str(ROOT / "csrc/capi/splatt.h"),
                     str(ROOT / "csrc/capi/splatt_main.cpp")])
     if not lib.exists() or lib.stat().st_mtime < newest:
         # capi_gpu.cpp is host-only HIP-API code: g++ with the AMD platform
@@ -97,6 +101,7 @@ ext = CppExtension(
     sources=[str(p.relative_to(ROOT)) for p in CORE_SOURCES]
     + ["csrc/pybind.cpp"],
     include_dirs=[str(ROOT / "csrc")],
+    depends=[str(LAUNCHERS_HPP.relative_to(ROOT))],
     extra_compile_args=["-O3", "-std=c++17", "-fopenmp", "-march=native"],
     extra_objects=hip_objs,
     extra_link_args=["-fopenmp", f"-L{ROCM}/lib", "-lamdhip64",

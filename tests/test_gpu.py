@@ -721,3 +721,119 @@ def test_gpu_bench_harness_lds_alg(t3):
     r = bench_mttkrp(t3, 16, ["flat", "lds"], 2, device="cuda",
                      validate=True)
     assert r["flat"]["validated"] and r["lds"]["validated"]
+
+
+# ------------------------------------------------------------------------
+# One case per launcher x element type that nothing above drives, at the
+# smallest shapes that still take each path: [40, 30, 150] with 2400
+# nonzeros (SPLATT_LDS_KB=1 cuts the 150-row mode into three 64-row LDS
+# buckets, one block each), rank 8 for the specialised kernels and rank 5
+# for the generic ones.
+
+SMALL_DIMS = [40, 30, 150]
+
+
+@pytest.fixture(scope="module")
+def small3():
+    """(tensor, {rank: (f64 factors, f64 oracle per mode, f32 bound per
+    mode)}). The bound is test_gpu_mttkrp_f32's 2e-2, tightened elementwise
+    by the forward bound of an f32 sum of products in any order:
+    |err| <= k u sum|terms| with u = 2^-24 and k < nnz + 2 nmodes roundings
+    per term (value, factor entries, products) and per partial sum."""
+    t = sp.SpTensor.synthetic(SMALL_DIMS, 2400, seed=5)
+    tabs = sp.SpTensor(t.inds, t.vals.abs(), t.dims)
+    k = t.nnz + 2 * t.nmodes
+    cases = {}
+    for rank in (8, 5):
+        mats_c = make_mats(t.dims, rank)
+        refs = [sp.mttkrp_stream(t, mats_c, m) for m in range(3)]
+        mags = [sp.mttkrp_stream(tabs, [a.abs() for a in mats_c], m)
+                for m in range(3)]
+        bounds = [torch.clamp(k * 2.0 ** -24 * g, max=2e-2) for g in mags]
+        cases[rank] = (mats_c, refs, bounds)
+    return t, cases
+
+
+def _as_f32(t, mats_c):
+    return (sp.SpTensor(t.inds, t.vals.float(), t.dims).to("cuda"),
+            [m.float().cuda() for m in mats_c])
+
+
+def _assert_f32_close(out, ref, bound, what):
+    assert out.dtype == torch.float32
+    err = (out.double().cpu() - ref).abs()
+    print(f"{what}: max err {float(err.max()):.3e}, "
+          f"max err/bound {float((err / bound.clamp(min=1e-300)).max()):.3e}")
+    assert bool((err <= bound).all()), what
+
+
+@pytest.mark.parametrize("alg,policy,rank", [("csf", "one", 8),
+                                             ("csf", "one", 5),
+                                             ("flat", "two", 5)])
+def test_gpu_mttkrp_f32_small(small3, alg, policy, rank):
+    """f32 through gpu_mttkrp3 (root/internal/leaf of one CSF; spec and
+    generic kernels) and through the generic-rank flat kernel."""
+    t, cases = small3
+    mats_c, refs, bounds = cases[rank]
+    t32, mats_g = _as_f32(t, mats_c)
+    cs = sp.csf_alloc(t32, policy)
+    for mode in range(3):
+        out = sp.mttkrp(cs, mats_g, mode, alg=alg)
+        _assert_f32_close(out, refs[mode], bounds[mode], (alg, rank, mode))
+
+
+@pytest.mark.parametrize("packed", [True, False], ids=["flat6", "flat5"])
+def test_gpu_lds_staged_f32_small(small3, monkeypatch, packed):
+    """f32 through the LDS-staged kernels, packed and separate streams."""
+    from splatt_amd.parallel.dist_cpd import build_shard_csf
+    t, cases = small3
+    mats_c, refs, bounds = cases[8]
+    t32, mats_g = _as_f32(t, mats_c)
+    monkeypatch.setenv("SPLATT_LDS_KB", "1")
+    cs = build_shard_csf(t32, SMALL_DIMS, "all", flat_only=True, stage_rank=8)
+    assert all(getattr(c, "_pack", None) is not None for c in cs.csfs)
+    assert any(c._stage["nbuckets"] == 3 for c in cs.csfs)
+    if not packed:
+        monkeypatch.setenv("SPLATT_NO_PACK", "1")
+    for mode in range(3):
+        out = sp.mttkrp(cs, mats_g, mode)
+        _assert_f32_close(out, refs[mode], bounds[mode], (packed, mode))
+
+
+@pytest.mark.parametrize("staged", [True, False], ids=["det6", "flat_det"])
+def test_gpu_deterministic_f32_small(small3, monkeypatch, staged):
+    """f32 through both deterministic kernels: oracle + bitwise repeat."""
+    from splatt_amd.parallel.dist_cpd import build_shard_csf
+    t, cases = small3
+    mats_c, refs, bounds = cases[8]
+    t32, mats_g = _as_f32(t, mats_c)
+    if staged:
+        monkeypatch.setenv("SPLATT_LDS_KB", "1")
+        cs = build_shard_csf(t32, SMALL_DIMS, "all", flat_only=True,
+                             stage_rank=8)
+        assert all(getattr(c, "_pack", None) is not None for c in cs.csfs)
+    else:
+        cs = sp.csf_alloc(t32, "all")
+    for mode in range(3):
+        out = sp.mttkrp(cs, mats_g, mode, deterministic=True).clone()
+        _assert_f32_close(out, refs[mode], bounds[mode], (staged, mode))
+        again = sp.mttkrp(cs, mats_g, mode, deterministic=True)
+        assert torch.equal(out, again), mode
+
+
+def test_gpu_lds_staged_5mode():
+    """Five modes: the staged separate-stream kernel with four other modes
+    (no packed stream above four modes)."""
+    from splatt_amd.parallel.dist_cpd import build_shard_csf
+    t = sp.SpTensor.synthetic([8, 12, 9, 11, 10], 2000, seed=7)
+    mats_c = make_mats(t.dims, 8)
+    mats_g = [m.cuda() for m in mats_c]
+    cs = build_shard_csf(t.to("cuda"), list(t.dims), "all", flat_only=True,
+                         stage_rank=8)
+    for c in cs.csfs:
+        assert getattr(c, "_stage", None) is not None
+        assert getattr(c, "_pack", None) is None
+    for mode in range(5):
+        out = sp.mttkrp(cs, mats_g, mode)
+        ref = sp.mttkrp_stream(t, mats_c, mode)
+        assert (out.cpu() - ref).abs().max().item() < 1e-8, mode
