@@ -52,4 +52,41 @@ std::vector<int64_t> partition_simple(int64_t n, int nparts) {
   return parts;
 }
 
+Strips plan_strips(const int64_t * rowptr, int64_t nrows, int64_t tile_rows,
+                   int64_t nnz_cap) {
+  Strips s;
+  if (tile_rows < 1) tile_rows = 1;
+  if (nnz_cap < 1) nnz_cap = 1;
+  int64_t r = 0;
+  int64_t p = 0;      // stream position; inside row r when that row is split
+  while (r < nrows) {
+    const int64_t first = r, start = p;
+    int flags = p > rowptr[r] ? 1 : 0;
+    int64_t n = 0, load = 0;
+    while (r < nrows && n < tile_rows) {
+      const int64_t rem = rowptr[r + 1] - p;
+      if (load + rem <= nnz_cap) {          // the rest of the row fits
+        load += rem;
+        p = rowptr[r + 1];
+        ++r;
+        ++n;
+      } else if (n == 0) {                  // heavier than the cap: split
+        load = nnz_cap;
+        p += nnz_cap;
+        n = 1;
+        flags |= 2;
+        break;
+      } else {
+        break;                              // starts the next strip
+      }
+    }
+    s.row0.push_back((int32_t)first);
+    s.nrows.push_back((int32_t)n);
+    s.flags.push_back(flags);
+    s.p0.push_back(start);
+    s.p1.push_back(p);
+  }
+  return s;
+}
+
 }  // namespace splatt

@@ -102,6 +102,36 @@ int mttkrp_flat6(const int32_t * pack, const S * const * mats,
                  int64_t nblocks, int32_t chunk, int32_t dim0, V * out,
                  int rank, int nother, void * stream);
 
+// -------------------------------------------------- mttkrp_strip.hip
+// Strip/window flat MTTKRP, root output of a strip-layout stream (f64
+// compute, factors and output; VS in {double, float} as for mttkrp_flat).
+// One workgroup per strip s in [0, nstrips): output rows
+// [s_row0[s], s_row0[s] + s_nrows[s]), s_nrows[s] <= tile_rows, accumulate
+// in an LDS tile and are then written to `out`; s_flags[s] bit 0 / bit 1:
+// the first / last row is shared with a neighbouring strip and is added
+// atomically, so `out` must be pre-zeroed. s_bounds: nstrips x (ngroups + 1)
+// stream positions, row s non-decreasing: launch g of a pass walks
+// [s_bounds[s][g], s_bounds[s][g + 1]) of each of its strips, launch 0
+// stores the unshared rows and the later ones add to them. key: int32
+// output row per nonzero; idx/mats: tables of at least 3, entries
+// [0, nother) used, nother in 2..3, the window level first (the order only
+// matters for speed). The strips run in passes of `wgs`
+// workgroups, ngroups launches each. -1 = rank outside {16,32,64}, nother
+// outside 2..3 or a stream not aligned to 128 B; -2 = the tile,
+// tile_rows * (rank + 2) * 8 bytes, exceeds the device's LDS limit.
+template <typename VS>
+int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
+                 const double * const * mats, const VS * vals,
+                 const int32_t * s_row0, const int32_t * s_nrows,
+                 const int32_t * s_flags, const int64_t * s_bounds,
+                 int ngroups, int64_t nstrips, int tile_rows, int wgs,
+                 double * out, int rank, int nother, void * stream);
+// Workgroups of that kernel instance resident at once on the current device
+// (occupancy x compute units): the default `wgs`. 0 when the instance does
+// not exist or the tile does not fit. Not for use during stream capture;
+// calling it first also keeps mttkrp_strip free of attribute calls.
+int strip_wgs(int rank, int nother, bool vals32, int tile_rows);
+
 // ---------------------------------------------------- mttkrp_det.hip
 // Bitwise-deterministic MTTKRP, V in {double, float}. `out` ([rows, rank],
 // pre-zeroed) is written with plain stores, no atomics. -1 = rank outside

@@ -1,0 +1,347 @@
+// Strip/window flat MTTKRP: root output kept in LDS, one gather served
+// from L2.
+//
+// The unstaged v7 kernel (mttkrp_flat.hip) misses L2 on every factor-row
+// gather when the factors are far larger than the 4 MiB per-XCD L2: two
+// 128-B lines per nonzero at rank 16 f64 and 3 modes. Bucketing the stream
+// by a gathered mode's row range makes that mode's rows L2-resident, but
+// with output in global memory every (output row, bucket) run costs an
+// atomic, and L2-sized buckets shred the runs. Here the output rows of a
+// workgroup live in LDS for the whole walk, so the bucket count costs
+// nothing in global memory:
+//
+//   strip   a contiguous range of at most tile_rows output rows and the
+//           stream range [p0, p1) of their nonzeros (planned on the host,
+//           csrc/core/partition.cpp plan_strips; nnz-balanced, a row heavier
+//           than the cap is split between strips and flagged as shared);
+//   window  inside a strip the nonzeros are sorted by idx_w / window_rows of
+//           one gathered level w (splatt_amd/csf.py), so at any moment the
+//           workgroups of a launch gather level w from one or two windows of
+//           its factor that fit the L2.
+//
+// One workgroup owns one strip: it zeroes a tile of tile_rows x F doubles
+// (row stride padded by 16 B), walks the strip's stream once in stored
+// order and stores the tile to `out` — plain coalesced stores, except the
+// rows it shares with a neighbouring strip, which are added atomically into
+// the pre-zeroed `out`. Per nonzero the work is v7's: a column group of F
+// lanes stages a 32-nonzero window of every stream with one non-temporal
+// load per 128-B line, redistributes it with __shfl, gathers in batches of
+// 8 (the window level, idx[0] / mats[0], with plain loads; the other levels,
+// whose rows miss anyway, non-temporally, so that they are the first lines
+// the L2 gives up) and folds consecutive nonzeros of one output row in a
+// register; on a
+// row change the partial goes to the tile with an LDS f64 add. The groups
+// of a workgroup take the strip's windows round-robin, so the workgroup
+// advances through the buckets together (2048 nonzeros per round at rank
+// 16).
+//
+// Launches: the strips run in passes of `wgs` workgroups, and a pass in
+// `ngroups` launches, launch g walking the g-th group of windows of every
+// strip of the pass (bounds[s][g] .. bounds[s][g + 1]). Workgroups drift
+// apart by far more than the time one of them spends in a window (measured,
+// profiles/amazon_strip_window.md), so inside one long launch they do not
+// share a window; the launch boundary is the synchronisation that keeps the
+// workgroups of a pass within one group of windows. The tile lives for one
+// launch: launch 0 stores it, later ones add it to the rows with a plain
+// read-modify-write (a strip's unshared rows belong to one workgroup, and
+// the in-order stream orders the launches).
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include <type_traits>
+
+#include "device_common.hpp"
+#include "launchers.hpp"
+
+namespace {
+
+constexpr int STRIP_THREADS = 1024;   // 16 waves: 4 per SIMD, one block/CU
+constexpr int STRIP_PAD = 2;          // doubles added to the tile row stride
+
+template <typename T, int N>
+__device__ __forceinline__ void ldnt_vec(const T * p, T (&r)[N]) {
+  if constexpr (N == 1) {
+    r[0] = ldnt(p);
+  } else {
+    using VT = T __attribute__((ext_vector_type(N)));
+    const VT v = __builtin_nontemporal_load(reinterpret_cast<const VT *>(p));
+    #pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = v[i];
+  }
+}
+
+// the strip descriptors (device arrays of nstrips entries) and the streams
+struct StripArgs {
+  const int32_t * key, * i0, * i1, * i2;
+  const double * m0, * m1, * m2;
+  const int32_t * row0, * nrows, * flags;
+  const int64_t * bounds;      // [nstrips][ngroups + 1] stream positions
+  int ngroups;
+};
+
+template <int F, int NOTHER, typename VS>
+__global__ void __launch_bounds__(STRIP_THREADS)
+mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
+                  int64_t strip0, int grp, int tile_rows,
+                  double * __restrict__ out) {
+  constexpr int R = WAVE / F;
+  constexpr int W = 32;                          // stream window (nnz)
+  constexpr int EPL = (F >= W) ? 1 : W / F;      // int32 elements per lane
+  constexpr int VPL = (sizeof(VS) == 8 && EPL > 1) ? EPL / 2 : EPL;
+  constexpr int NVL = EPL / VPL;                 // vals loads per window
+  constexpr int CH = W / NVL;                    // elements per vals load
+  constexpr int GB = 8;                          // gather sub-batch
+  constexpr int LD = F + STRIP_PAD;              // tile row stride
+  extern __shared__ double tile[];
+
+  const int32_t * __restrict__ key = a.key;
+  const int32_t * __restrict__ i0 = a.i0;
+  const int32_t * __restrict__ i1 = a.i1;
+  const int32_t * __restrict__ i2 = a.i2;
+  const double * __restrict__ m0 = a.m0;
+  const double * __restrict__ m1 = a.m1;
+  const double * __restrict__ m2 = a.m2;
+
+  const int64_t s = strip0 + blockIdx.x;
+  const int32_t row0 = a.row0[s];
+  const int nr = a.nrows[s] < tile_rows ? a.nrows[s] : tile_rows;
+  const int fl = a.flags[s];
+  const int64_t * bnd = a.bounds + s * (a.ngroups + 1) + grp;
+  const int64_t p0 = bnd[0], p1 = bnd[1];
+
+  for (int e = threadIdx.x; e < nr * LD; e += blockDim.x) tile[e] = 0.0;
+  __syncthreads();
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = lane % F;
+  const int g = lane / F;
+  const int gbase = g * F;
+  const int slot = c & (W / EPL - 1);            // F=64: lanes 32.. mirror
+  const int ngroups = (blockDim.x / WAVE) * R;
+  const int gid = (threadIdx.x / WAVE) * R + g;
+
+  int32_t cur = -1;
+  double acc = 0.0;
+  // a row outside the strip (a stream that does not match its descriptors)
+  // is dropped, never written past the tile
+  auto flush = [&]() {
+    const uint32_t lr = (uint32_t)(cur - row0);
+    if (lr < (uint32_t)nr) unsafeAtomicAdd(&tile[lr * LD + c], acc);
+  };
+  auto fold = [&](int32_t k, double x) {
+    if (k != cur) {
+      flush();
+      acc = 0.0;
+      cur = k;
+    }
+    acc += x;
+  };
+  // one element at a time, every lane of the group reading the same words
+  auto scalar = [&](int64_t pa, int64_t pb) {
+    for (int64_t p = pa; p < pb; ++p) {
+      double x = (double)ldnt(&vals[p]) * m0[(int64_t)ldnt(&i0[p]) * F + c]
+                 * ldnt(&m1[(int64_t)ldnt(&i1[p]) * F + c]);
+      if constexpr (NOTHER > 2)
+        x *= ldnt(&m2[(int64_t)ldnt(&i2[p]) * F + c]);
+      fold(ldnt(&key[p]), x);
+    }
+  };
+
+  // windows are the 128-B lines of the streams (all 128-B aligned): whole
+  // windows [wa, wb) of the strip go round-robin over the groups, the
+  // partial ones at its two ends to the first and the last group
+  const int64_t wa = (p0 + W - 1) / W, wb = p1 / W;
+  const int64_t he = min64(p1, wa * W);
+  const int64_t ts = he > wb * W ? he : wb * W;
+  if (gid == 0) scalar(p0, he);
+
+  for (int64_t w = wa + gid; w < wb; w += ngroups) {
+    const int64_t pw = w * W;
+    const int64_t ps = pw + slot * EPL;
+    int32_t kreg[EPL], i0reg[EPL], i1reg[EPL], i2reg[EPL];
+    VS vreg[NVL][VPL];
+    ldnt_vec(key + ps, kreg);
+    ldnt_vec(i0 + ps, i0reg);
+    ldnt_vec(i1 + ps, i1reg);
+    if constexpr (NOTHER > 2) ldnt_vec(i2 + ps, i2reg);
+    #pragma unroll
+    for (int k = 0; k < NVL; ++k)
+      ldnt_vec(vals + pw + k * CH + slot * VPL, vreg[k]);
+    #pragma unroll
+    for (int k = 0; k < NVL; ++k) {
+      #pragma unroll 1
+      for (int h = 0; h < CH; h += GB) {
+        const int ub = k * CH + h;
+        double vv[GB], a0[GB], a1[GB], a2[GB];
+        #pragma unroll
+        for (int u = 0; u < GB; ++u) {
+          const int src = gbase + ub / EPL + u / EPL;
+          vv[u] = (double)__shfl(vreg[k][u % VPL], gbase + h / VPL + u / VPL,
+                                 WAVE);
+          const int32_t j0 = __shfl(i0reg[u % EPL], src, WAVE);
+          const int32_t j1 = __shfl(i1reg[u % EPL], src, WAVE);
+          a0[u] = m0[(int64_t)j0 * F + c];
+          a1[u] = ldnt(&m1[(int64_t)j1 * F + c]);
+          if constexpr (NOTHER > 2) {
+            const int32_t j2 = __shfl(i2reg[u % EPL], src, WAVE);
+            a2[u] = ldnt(&m2[(int64_t)j2 * F + c]);
+          }
+        }
+        #pragma unroll
+        for (int u = 0; u < GB; ++u) {
+          double x = vv[u] * a0[u] * a1[u];
+          if constexpr (NOTHER > 2) x *= a2[u];
+          fold(__shfl(kreg[u % EPL], gbase + ub / EPL + u / EPL, WAVE), x);
+        }
+      }
+    }
+  }
+
+  if (gid == ngroups - 1) scalar(ts, p1);
+  flush();
+  __syncthreads();
+
+  for (int e = threadIdx.x; e < nr * F; e += blockDim.x) {
+    const int lr = e / F, cc = e % F;
+    const double v = tile[lr * LD + cc];
+    double * o = &out[(int64_t)(row0 + lr) * F + cc];
+    if ((lr == 0 && (fl & 1)) || (lr == nr - 1 && (fl & 2)))
+      atomic_add_g(o, v);
+    else if (grp == 0)
+      *o = v;
+    else
+      *o += v;             // the strip's rows are this workgroup's alone
+  }
+}
+
+// largest dynamic LDS request a block may make on the current device
+inline int lds_limit() {
+  static int limit = -1;
+  if (limit < 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock,
+                                 dev) != hipSuccess)
+      return 0;
+    limit = v;
+  }
+  return limit;
+}
+
+inline int cu_count() {
+  static int n = -1;
+  if (n < 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                                 dev) != hipSuccess)
+      return 0;
+    n = v;
+  }
+  return n;
+}
+
+struct StripLaunch {
+  StripArgs a;
+  const void * vals;
+  int64_t nstrips;
+  int wgs;
+  int tile_rows;
+  double * out;
+  hipStream_t st;
+};
+
+// One kernel instance: raise its dynamic-LDS limit to `lds` bytes (once per
+// size), then either answer the resident-workgroup count (L == nullptr) or
+// launch the passes.
+template <int F, int NOTHER, typename VS>
+int strip_inst(const StripLaunch * L, int lds, int * wgs) {
+  static int lds_set = 0;
+  auto kern = mttkrp_strip_kern<F, NOTHER, VS>;
+  if (lds > lds_set) {
+    const hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void *>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return (int)e;
+    lds_set = lds;
+  }
+  if (!L) {
+    int per_cu = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, kern, STRIP_THREADS, (size_t)lds);
+    if (e != hipSuccess) return (int)e;
+    *wgs = per_cu * cu_count();
+    return 0;
+  }
+  for (int64_t s0 = 0; s0 < L->nstrips; s0 += L->wgs) {
+    const int64_t n = L->nstrips - s0 < L->wgs ? L->nstrips - s0 : L->wgs;
+    for (int g = 0; g < L->a.ngroups; ++g)
+      hipLaunchKernelGGL(kern, dim3((uint32_t)n), dim3(STRIP_THREADS),
+                         (size_t)lds, L->st, L->a,
+                         static_cast<const VS *>(L->vals), s0, g,
+                         L->tile_rows, L->out);
+  }
+  return launch_rc();
+}
+
+template <typename VS>
+int strip_dispatch(const StripLaunch * L, int tile_rows, int rank, int nother,
+                   int * wgs) {
+  if (!(rank == 16 || rank == 32 || rank == 64) || nother < 2 || nother > 3
+      || tile_rows < 1)
+    return -1;
+  const int64_t lds = (int64_t)tile_rows * (rank + STRIP_PAD) * 8;
+  if (lds > lds_limit()) return -2;
+#define SI(F_, N_) return strip_inst<F_, N_, VS>(L, (int)lds, wgs)
+#define SF(N_) \
+  switch (rank) { case 16: SI(16, N_); case 32: SI(32, N_); \
+                  default: SI(64, N_); }
+  if (nother == 2) { SF(2); }
+  SF(3);
+#undef SF
+#undef SI
+}
+
+}  // namespace
+
+namespace splatt {
+namespace hip {
+
+int strip_wgs(int rank, int nother, bool vals32, int tile_rows) {
+  int wgs = 0;
+  const int rc = vals32
+      ? strip_dispatch<float>(nullptr, tile_rows, rank, nother, &wgs)
+      : strip_dispatch<double>(nullptr, tile_rows, rank, nother, &wgs);
+  return rc == 0 ? wgs : 0;
+}
+
+template <typename VS>
+int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
+                 const double * const * mats, const VS * vals,
+                 const int32_t * s_row0, const int32_t * s_nrows,
+                 const int32_t * s_flags, const int64_t * s_bounds,
+                 int ngroups, int64_t nstrips, int tile_rows, int wgs,
+                 double * out, int rank, int nother, void * stream) {
+  if (nstrips <= 0) return 0;
+  if (wgs < 1 || ngroups < 1 || nother < 2 || nother > 3) return -1;
+  // windows are the streams' 128-B lines
+  uintptr_t bits = (uintptr_t)key | (uintptr_t)vals;
+  for (int t = 0; t < nother; ++t) bits |= (uintptr_t)idx[t];
+  if (bits & 127) return -1;
+  StripLaunch L{{key, idx[0], idx[1], nother > 2 ? idx[2] : nullptr, mats[0],
+                 mats[1], nother > 2 ? mats[2] : nullptr, s_row0, s_nrows,
+                 s_flags, s_bounds, ngroups},
+                vals, nstrips, wgs, tile_rows, out, (hipStream_t)stream};
+  return strip_dispatch<VS>(&L, tile_rows, rank, nother, nullptr);
+}
+
+#define STRIP_SIG(VS)                                                      \
+  const int32_t *, const int32_t * const *, const double * const *,        \
+  const VS *, const int32_t *, const int32_t *, const int32_t *,           \
+  const int64_t *, int, int64_t, int, int, double *, int, int, void *
+template int mttkrp_strip<double>(STRIP_SIG(double));
+template int mttkrp_strip<float>(STRIP_SIG(float));
+#undef STRIP_SIG
+
+}  // namespace hip
+}  // namespace splatt

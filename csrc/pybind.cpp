@@ -576,6 +576,75 @@ static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
   return rc == 0;
 }
 
+// Strip/window flat MTTKRP (csrc/hip/mttkrp_strip.hip): the strip
+// descriptors of splatt_amd/csf.py (device arrays), f64 or f32 value stream,
+// f64 factors and output. Returns false when the launcher declines
+// (misaligned streams, tile above the LDS limit) — the caller then takes the
+// key-stream kernel.
+static bool py_mttkrp_strip_gpu(Tensor key, std::vector<Tensor> idx,
+                                std::vector<Tensor> mats, Tensor vals,
+                                Tensor s_row0, Tensor s_nrows, Tensor s_flags,
+                                Tensor s_bounds, int64_t tile_rows,
+                                int64_t wgs, Tensor out, int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 3, "strip kernel supports 3..4 modes");
+  TORCH_CHECK(tile_rows >= 1 && tile_rows <= (1 << 20) && wgs >= 1
+              && wgs <= (1 << 20), "tile_rows / wgs out of range");
+  const int64_t nnz = vals.numel();
+  const int rank = rank_of(mats);
+  double * op = out_ptr<double>(out, rank);
+  auto ip = stream_table(idx, nother, nnz);
+  auto mp = factor_table<double>(mats, nother, rank);
+  const int32_t * kp = dev_ptr<int32_t>(key, "key");
+  TORCH_CHECK(key.numel() == nnz, "key must be int32 of nnz entries");
+  const int32_t * r0 = dev_ptr<int32_t>(s_row0, "strip row0");
+  const int32_t * nr = dev_ptr<int32_t>(s_nrows, "strip nrows");
+  const int32_t * fl = dev_ptr<int32_t>(s_flags, "strip flags");
+  const int64_t * bp = dev_ptr<int64_t>(s_bounds, "strip bounds");
+  const int64_t ns = s_row0.numel();
+  TORCH_CHECK(s_nrows.numel() == ns && s_flags.numel() == ns
+              && s_bounds.dim() == 2 && s_bounds.size(0) == ns
+              && s_bounds.size(1) >= 2 && s_bounds.size(1) <= (1 << 16),
+              "strip descriptor lengths differ");
+  const int ng = (int)s_bounds.size(1) - 1;
+  const int rc = vals.scalar_type() == torch::kFloat32
+      ? gpu::mttkrp_strip<float>(kp, ip.data(), mp.data(),
+                                 dev_ptr<float>(vals, "vals"), r0, nr, fl, bp,
+                                 ng, ns, (int)tile_rows, (int)wgs, op, rank,
+                                 (int)nother, (void *)stream)
+      : gpu::mttkrp_strip<double>(kp, ip.data(), mp.data(),
+                                  dev_ptr<double>(vals, "vals"), r0, nr, fl,
+                                  bp, ng, ns, (int)tile_rows, (int)wgs, op,
+                                  rank, (int)nother, (void *)stream);
+  if (rc > 0) check_rc(rc, "strip MTTKRP");
+  return rc == 0;
+}
+
+// strips of a root-sorted stream (core/partition.hpp plan_strips): rowptr is
+// a host int64 tensor of rows + 1 entries
+static py::dict py_plan_strips(Tensor rowptr, int64_t tile_rows,
+                               int64_t nnz_cap) {
+  TORCH_CHECK(!rowptr.is_cuda() && rowptr.scalar_type() == torch::kInt64
+              && rowptr.is_contiguous() && rowptr.numel() >= 1,
+              "rowptr must be a contiguous host int64 tensor");
+  TORCH_CHECK(tile_rows >= 1 && nnz_cap >= 1, "tile_rows, nnz_cap >= 1");
+  const sp::Strips s = sp::plan_strips(rowptr.data_ptr<int64_t>(),
+                                       rowptr.numel() - 1, tile_rows, nnz_cap);
+  auto t32 = [](const std::vector<int32_t> & v) {
+    return torch::tensor(v, torch::kInt32);
+  };
+  auto t64 = [](const std::vector<int64_t> & v) {
+    return torch::tensor(v, torch::kInt64);
+  };
+  py::dict d;
+  d["row0"] = t32(s.row0);
+  d["nrows"] = t32(s.nrows);
+  d["flags"] = t32(s.flags);
+  d["p0"] = t64(s.p0);
+  d["p1"] = t64(s.p1);
+  return d;
+}
+
 // deterministic flat MTTKRP (csrc/hip/mttkrp_det.hip): plain stores for
 // walker-interior key runs + ordered fixup of boundary partials in `side`
 static void py_gpu_mttkrp_flat_det(Tensor key, std::vector<Tensor> idx,
@@ -1076,6 +1145,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gpu_mttkrp_flat_v32", &py_gpu_mttkrp_flat_v32,
         "flat MTTKRP (v7) reading an f32 copy of f32-exact f64 values, by "
         "row pointers or key stream; false = declined, use the f64 stream");
+  m.def("mttkrp_strip_gpu", &py_mttkrp_strip_gpu,
+        "strip/window flat MTTKRP (root output in LDS tiles over a "
+        "strip-layout stream); false = declined, use gpu_mttkrp_flat");
+  m.def("strip_wgs", &gpu::strip_wgs,
+        "resident workgroups of a strip kernel instance on this device "
+        "(rank, nother, f32 values, tile rows); 0 = no such instance");
+  m.def("plan_strips", &py_plan_strips,
+        "strips of a root-sorted stream: row0/nrows/flags/p0/p1 (host)");
   m.def("gpu_mttkrp_flat_det", &py_gpu_mttkrp_flat_det,
         "bitwise-deterministic flat MTTKRP (depth-0 streams, spec ranks)");
   m.def("flat_det_ws_elems", &gpu::flat_det_ws,

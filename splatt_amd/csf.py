@@ -82,6 +82,12 @@ class Csf:
         stage = getattr(self, "_stage", None)
         if stage is not None:
             object.__setattr__(c, "_stage", dict(stage))
+        # strip/window layout (build_csf): sizes + descriptor tensors
+        strip = getattr(self, "_strip", None)
+        if strip is not None:
+            object.__setattr__(c, "_strip", {
+                k: v.to(device) if isinstance(v, torch.Tensor) else v
+                for k, v in strip.items()})
         # root row pointers of the flat kernel (mttkrp.py _root_rowptr)
         rowptr = getattr(self, "_rowptr", None)
         if rowptr is not None:
@@ -170,9 +176,102 @@ def order_modes(dims: Sequence[int], policy: str, mode: int = 0) -> List[int]:
     return [int(x) for x in native().order_modes(list(dims), policy, mode)]
 
 
+L2_BYTES = 4 << 20          # one XCD's L2
+
+
+def strip_gate(dims: Sequence[int], perm: Sequence[int], nnz: int,
+               stage_rank: int, wgs: int = 256, tile_kb: int = 128,
+               window_kb: int = 1024) -> Optional[dict]:
+    """Line-count model of the strip/window layout (csrc/hip/
+    mttkrp_strip.hip) against the unstaged v7 kernel for the root-output CSF
+    with level order `perm`; the chosen sizes, or None when the layout is
+    not worth building. Lines are 128-B L2 misses per nonzero, f64 factors:
+
+        v7     NOTHER * rowlines + 12/128
+        strip  (NOTHER - 1) * rowlines + 16/128
+               + passes * 8 * dims[w] * rowlines / nnz
+
+    rowlines = rank * 8 / 128 lines of a factor row, passes = ceil(strips /
+    wgs) launches, and the last term every XCD re-reading the window mode's
+    factor once per pass. A window level w is eligible when its factor is at
+    least 4x the L2 (smaller ones already hit); the one with the smallest
+    refetch term is taken, and the layout is chosen when the model predicts
+    at most 0.8x the lines of v7. A tensor with fewer strips than one launch
+    holds (`wgs`) is left alone: its workgroups would not fill the device,
+    which the line model does not see."""
+    nm = len(dims)
+    if stage_rank <= 0 or not 3 <= nm <= 4 or nnz <= 0:
+        return None
+    rowbytes = stage_rank * 8
+    rowlines = rowbytes / 128.0
+    tile_rows = max(1, tile_kb * 1024 // rowbytes)
+    window_rows = max(1, window_kb * 1024 // rowbytes)
+    nstrips = -(-dims[perm[0]] // tile_rows)
+    if nstrips < wgs:
+        return None
+    passes = -(-nstrips // wgs)
+    best = None
+    for l in range(1, nm):
+        d = dims[perm[l]]
+        if d * rowbytes < 4 * L2_BYTES:
+            continue
+        refetch = passes * 8 * d * rowlines / nnz
+        if best is None or refetch < best[1]:
+            best = (l, refetch)
+    if best is None:
+        return None
+    nother = nm - 1
+    v7 = nother * rowlines + 12 / 128.0
+    new = (nother - 1) * rowlines + 16 / 128.0 + best[1]
+    if new > 0.8 * v7:
+        return None
+    return {"level": best[0], "tile_rows": tile_rows,
+            "window_rows": window_rows, "wgs": wgs, "passes": passes,
+            "lines_v7": v7, "lines_strip": new}
+
+
+def strip_layout(root: torch.Tensor, widx: torch.Tensor, nrows: int,
+                 wdim: int, tile_rows: int, nnz_cap: int,
+                 window_rows: int, groups: int = 1) -> tuple:
+    """Strips and the strip/window order of a root-sorted stream. `root` is
+    the non-decreasing output row per nonzero, `widx` the window level's
+    index in the same order. Returns (strips, order): `strips` the host
+    descriptors of plan_strips (every nonzero in exactly one strip, strips
+    within the row and nnz caps, a row heavier than the cap split and
+    flagged), `order` the permutation that stably sorts the stream by
+    (strip, widx // window_rows) — inside a (strip, window) cell the order
+    stays (row, remaining levels). strips["bounds"] ([strips, groups + 1])
+    cuts every strip's range at the same `groups` + 1 window boundaries:
+    one launch of the kernel walks one group of windows of its strips."""
+    dev = root.device
+    rowptr = torch.searchsorted(
+        root.contiguous(),
+        torch.arange(nrows + 1, dtype=root.dtype, device=dev)
+    ).to(torch.int64).cpu().contiguous()
+    strips = native().plan_strips(rowptr, int(tile_rows), int(nnz_cap))
+    ns = int(strips["row0"].numel())
+    nb = -(-wdim // window_rows)
+    kdt = torch.int32 if ns * nb < 2 ** 31 else torch.int64
+    lens = (strips["p1"] - strips["p0"]).to(dev)
+    cell = torch.repeat_interleave(
+        torch.arange(ns, dtype=kdt, device=dev) * nb, lens)
+    cell += torch.div(widx, window_rows, rounding_mode="floor").to(kdt)
+    strips["nbuckets"] = nb
+    cell, order = torch.sort(cell, stable=True)
+    groups = max(1, min(int(groups), nb))
+    edge = torch.tensor([-(-g * nb // groups) for g in range(groups + 1)],
+                        dtype=kdt, device=dev)
+    q = (torch.arange(ns, dtype=kdt, device=dev) * nb).unsqueeze(1) + edge
+    strips["bounds"] = torch.searchsorted(cell, q.reshape(-1).contiguous()) \
+        .to(torch.int64).reshape(ns, groups + 1).cpu()
+    return strips, order
+
+
 def build_csf(t: SpTensor, perm: Sequence[int], flat_only: bool = False,
               gather_tiles: int = 0, stage_rank: int = 0,
-              lds_kb: int = 0) -> Csf:
+              lds_kb: int = 0, strip_rows: int = 0, strip_cap: int = 0,
+              strip_window: int = 0, strip_wgs: int = 0,
+              strip_groups: int = 0) -> Csf:
     """Build one CSF with level->mode permutation `perm`. `flat_only`
     (device builds): skip the fptr/fids tree — the sorted columns ARE the
     flat kernel's expansions, so billion-nnz ALLMODE sets build ~2x faster
@@ -182,7 +281,16 @@ def build_csf(t: SpTensor, perm: Sequence[int], flat_only: bool = False,
     each phase's random factor-row gathers hit a 1/T-sized working set
     (reference tt_densetile's cache story, tile.c:262, recast for the
     per-XCD L2/L3 hierarchy). Output-key runs stay contiguous per bucket,
-    so the kernel is unchanged (one atomic per key run per bucket)."""
+    so the kernel is unchanged (one atomic per key run per bucket).
+    `stage_rank` > 0 whose LDS staging is declined (run-density gate) may
+    take the strip/window layout instead (strip_gate; SPLATT_STRIP=0
+    disables, SPLATT_STRIP_TILE_KB / _WINDOW_KB / _WGS size it).
+    `strip_rows` > 0 forces that layout with these sizes whatever the gate
+    says: rows per strip, `strip_cap` nonzeros per strip (0: the mean strip
+    load), `strip_window` rows of the window level per window (0: 1 MiB of
+    factor rows), `strip_wgs` workgroups per launch (0: what the device
+    holds), `strip_groups` launches per pass, each over one group of
+    windows (0: the default, STRIP_GROUP_KB of factor rows per group)."""
     if any(d > 0xFFFFFFFF for d in t.dims):
         raise ValueError("mode dimensions above 2^32 are not supported "
                          "(CSF node ids are 32-bit; shard the mode first)")
@@ -201,7 +309,9 @@ def build_csf(t: SpTensor, perm: Sequence[int], flat_only: bool = False,
             import os
             lds_kb = int(os.environ.get("SPLATT_LDS_KB", "24"))
         return _build_csf_device(t, list(perm), flat_only, gather_tiles,
-                                 stage_rank, lds_kb)
+                                 stage_rank, lds_kb,
+                                 (strip_rows, strip_cap, strip_window,
+                                  strip_wgs, strip_groups))
     d = native().csf_build(t.inds, t.vals, list(t.dims), list(perm))
     return Csf(dims=[int(x) for x in d["dims"]],
                dim_perm=[int(x) for x in d["dim_perm"]],
@@ -210,11 +320,78 @@ def build_csf(t: SpTensor, perm: Sequence[int], flat_only: bool = False,
                vals=d["vals"])
 
 
+def _strip_ok(t: SpTensor, stage_rank: int) -> bool:
+    """Tensors the strip kernel exists for: f64, 3 or 4 modes, a kernel
+    rank, and no deterministic build (that path needs contiguous keys)."""
+    import os
+    return (t.vals.dtype == torch.float64 and 3 <= t.nmodes <= 4
+            and stage_rank in (16, 32, 64)
+            and os.environ.get("SPLATT_DETERMINISTIC") != "1")
+
+
+def _strip_wgs(rank: int, nother: int, tile_rows: int) -> int:
+    """Workgroups per launch the device holds, for both value-stream types
+    (asking also prepares both kernel instances before any stream capture);
+    0 when the tile does not fit."""
+    return min(native().strip_wgs(rank, nother, v32, tile_rows)
+               for v32 in (False, True))
+
+
+# factor bytes of the window level per launch group: the workgroups of a
+# launch stay within this much of the factor (measured default,
+# profiles/amazon_strip_window.md); SPLATT_STRIP_GROUP_KB overrides
+STRIP_GROUP_KB = 16384
+
+
+def _strip_groups(factor_bytes: int) -> int:
+    import os
+    kb = int(os.environ.get("SPLATT_STRIP_GROUP_KB", str(STRIP_GROUP_KB)))
+    return max(1, -(-factor_bytes // (max(1, kb) * 1024)))
+
+
+def _strip_default(t: SpTensor, perm: List[int], stage_rank: int):
+    """The gate of a build whose LDS staging was declined: strip_gate with
+    the device's workgroup count and the SPLATT_STRIP_* knobs."""
+    import os
+    if os.environ.get("SPLATT_STRIP") == "0" or not _strip_ok(t, stage_rank):
+        return None
+    tile_kb = int(os.environ.get("SPLATT_STRIP_TILE_KB", "128"))
+    window_kb = int(os.environ.get("SPLATT_STRIP_WINDOW_KB", "1024"))
+    wgs = int(os.environ.get("SPLATT_STRIP_WGS", "0"))
+    tile_rows = max(1, tile_kb * 1024 // (stage_rank * 8))
+    held = _strip_wgs(stage_rank, t.nmodes - 1, tile_rows)
+    if held <= 0:
+        return None
+    return strip_gate(t.dims, perm, t.nnz, stage_rank, wgs if wgs > 0 else held,
+                      tile_kb, window_kb)
+
+
+def _strip_forced(t: SpTensor, perm: List[int], stage_rank: int,
+                  sizes: tuple) -> dict:
+    rows, cap, window, wgs, groups = (int(x) for x in sizes)
+    if not _strip_ok(t, stage_rank):
+        raise ValueError(
+            "the strip/window layout needs an f64 tensor of 3 or 4 modes, "
+            "stage_rank in {16,32,64} and a non-deterministic build")
+    w = max(range(1, t.nmodes), key=lambda l: t.dims[perm[l]])
+    if window <= 0:
+        window = max(1, (1 << 20) // (stage_rank * 8))
+    if wgs <= 0:
+        wgs = _strip_wgs(stage_rank, t.nmodes - 1, rows)
+        if wgs <= 0:
+            raise ValueError(f"a strip of {rows} rows at rank {stage_rank} "
+                             "does not fit the device's LDS")
+    return {"level": w, "tile_rows": rows, "window_rows": window,
+            "wgs": wgs, "cap": cap, "groups": groups}
+
+
 def _build_csf_device(t: SpTensor, perm: List[int],
                       flat_only: bool = False,
                       gather_tiles: int = 0, stage_rank: int = 0,
-                      lds_kb: int = 48) -> Csf:
+                      lds_kb: int = 48,
+                      strip_sizes: tuple = (0, 0, 0, 0, 0)) -> Csf:
     """All-device CSF construction with torch/rocPRIM primitives."""
+    stage_rank_in = stage_rank
     nm, nnz = t.nmodes, t.nnz
     dev = t.device
     if nnz == 0:
@@ -232,11 +409,15 @@ def _build_csf_device(t: SpTensor, perm: List[int],
         keys = t.inds[perm[level]].index_select(0, order)
         order = order.index_select(0, torch.argsort(keys, stable=True))
     stage_meta = None
+    strip_cfg = None
     cache_mb = 0
     if flat_only:
         import os as _os2
         cache_mb = int(_os2.environ.get("SPLATT_CACHE_TILE_MB", "0"))
-    if flat_only and cache_mb > 0 and stage_rank > 0:
+    if flat_only and strip_sizes[0] > 0:
+        # forced strip/window layout (tests, experiments): no staging
+        strip_cfg = _strip_forced(t, perm, stage_rank, strip_sizes)
+    elif flat_only and cache_mb > 0 and stage_rank > 0:
         # EXPERIMENTAL 3-D cache tiling for HBM-bound shapes: bucket by a
         # cell over ALL modes with per-mode factor windows <= cache_mb, so
         # every stream (output atomics + both gathers) works in an
@@ -289,6 +470,7 @@ def _build_csf_device(t: SpTensor, perm: List[int],
                     big, chunk, tiles = l, ch, ti
                     break
             if big < 0:
+                strip_cfg = _strip_default(t, perm, stage_rank)
                 stage_rank = 0
         else:
             dim_big = t.dims[perm[big]]
@@ -301,6 +483,29 @@ def _build_csf_device(t: SpTensor, perm: List[int],
         if stage_rank > 0:
             stage_meta = {"level": big, "chunk": int(chunk),
                           "nbuckets": int(tiles)}
+    strip_meta = None
+    if strip_cfg is not None:
+        w = strip_cfg["level"]
+        nrows = t.dims[perm[0]]
+        ns_rows = -(-nrows // strip_cfg["tile_rows"])
+        cap = strip_cfg.get("cap") or max(1, -(-nnz // ns_rows))
+        strips, sorder = strip_layout(
+            t.inds[perm[0]].index_select(0, order),
+            t.inds[perm[w]].index_select(0, order), nrows, t.dims[perm[w]],
+            strip_cfg["tile_rows"], cap, strip_cfg["window_rows"],
+            strip_cfg.get("groups") or _strip_groups(
+                t.dims[perm[w]] * stage_rank_in * 8))
+        order = order.index_select(0, sorder)
+        del sorder
+        # launches take the strips in this order: heaviest first, so the
+        # workgroups of one launch carry like loads and finish together
+        by_load = torch.argsort(strips["p1"] - strips["p0"], descending=True,
+                                stable=True)
+        strip_meta = dict(strip_cfg, cap=int(cap),
+                          nbuckets=int(strips["nbuckets"]))
+        strip_meta["groups"] = int(strips["bounds"].shape[1]) - 1
+        for k in ("row0", "nrows", "flags", "p0", "p1", "bounds"):
+            strip_meta[k] = strips[k].index_select(0, by_load).to(dev)
     sinds = [t.inds[perm[l]].index_select(0, order) for l in range(nm)]
     svals = t.vals.index_select(0, order)
 
@@ -329,6 +534,8 @@ def _build_csf_device(t: SpTensor, perm: List[int],
         object.__setattr__(c, "_expand_cache", cache)
         if stage_meta is not None:
             object.__setattr__(c, "_stage", stage_meta)
+        if strip_meta is not None:
+            object.__setattr__(c, "_strip", strip_meta)
         return c
 
     # new-node flags per level: node at level l starts where any of levels

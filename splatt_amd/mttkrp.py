@@ -356,6 +356,27 @@ def _gpu_mttkrp_flat(c: Csf, depth: int, mats: List[torch.Tensor],
             blocks["end"], blocks["row0"], blocks["chunk"],
             c.dims[c.dim_perm[lvl]], out, stream)
         return
+    strip = getattr(c, "_strip", None) if depth == 0 else None
+    if strip is not None:
+        # strip/window layout (csf.py build_csf): the root output goes
+        # through LDS tiles (csrc/hip/mttkrp_strip.hip). What that kernel
+        # has no instance for, or declines, runs on the key stream below.
+        if rows is not None:
+            raise ValueError("rows-restricted MTTKRP needs a key-sorted "
+                             "stream for this mode")
+        if rank in (16, 32, 64) and not storage and nm <= 4:
+            # window level first: the kernel keeps its rows in L2
+            lv = [strip["level"]] + [l for l in range(1, nm)
+                                     if l != strip["level"]]
+            idx = [c.ancestor_expand(l).contiguous() for l in lv]
+            ms = [mats[c.dim_perm[l]].contiguous() for l in lv]
+            v32 = _vals32(c, rank, mats)
+            if native().mttkrp_strip_gpu(
+                    key.contiguous(), idx, ms, c.vals if v32 is None else v32,
+                    strip["row0"], strip["nrows"], strip["flags"],
+                    strip["bounds"], strip["tile_rows"],
+                    strip["wgs"], out, stream):
+                return
     p0, p1 = 0, c.nnz
     if rows is not None:
         if not _key_sorted(c, depth):
@@ -411,6 +432,8 @@ def mttkrp_rows_ok(src: CsfSet | Csf, mode: int, rank: int) -> bool:
         return False
     if c.device.type == "cuda" and _use_lds(c, depth, rank):
         return True
+    if depth == 0 and getattr(c, "_strip", None) is not None:
+        return False          # strip/window order: not key-sorted
     return _key_sorted(c, depth)
 
 
