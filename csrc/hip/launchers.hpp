@@ -105,19 +105,29 @@ int mttkrp_flat6(const int32_t * pack, const S * const * mats,
 // -------------------------------------------------- mttkrp_strip.hip
 // Strip/window flat MTTKRP, root output of a strip-layout stream (f64
 // compute, factors and output; VS in {double, float} as for mttkrp_flat).
-// One workgroup per strip s in [0, nstrips): output rows
+// A strip s in [0, nstrips) is walked by one workgroup: output rows
 // [s_row0[s], s_row0[s] + s_nrows[s]), s_nrows[s] <= tile_rows, accumulate
 // in an LDS tile and are then written to `out`; s_flags[s] bit 0 / bit 1:
 // the first / last row is shared with a neighbouring strip and is added
 // atomically, so `out` must be pre-zeroed. s_bounds: nstrips x (ngroups + 1)
-// stream positions, row s non-decreasing: launch g of a pass walks
-// [s_bounds[s][g], s_bounds[s][g + 1]) of each of its strips, launch 0
-// stores the unshared rows and the later ones add to them. key: int32
-// output row per nonzero; idx/mats: tables of at least 3, entries
-// [0, nother) used, nother in 2..3, the window level first (the order only
-// matters for speed). The strips run in passes of `wgs`
-// workgroups, ngroups launches each. -1 = rank outside {16,32,64}, nother
-// outside 2..3 or a stream not aligned to 128 B; -2 = the tile,
+// stream positions, row s non-decreasing: group g of strip s is
+// [s_bounds[s][g], s_bounds[s][g + 1]), inside [0, nnz), the length of key,
+// idx and vals. key: int32 output row per nonzero;
+// idx/mats: tables of at least 3, entries [0, nother) used, nother in 2..3,
+// the window level first (the order only matters for speed). One launch of
+// min(wgs, nstrips) workgroups, workgroup b taking strips b, b + grid, ...;
+// `wgs` should not exceed strip_wgs(), or the grid is not co-resident.
+// `pace` (96 words, device, or null): after each group the workgroups wait
+// for each other on its arrival counter, each wait bounded by `pace_us`
+// microseconds of wall clock; the launcher zeroes the words on `stream`
+// first (a memset node under capture). After the launch word 0 holds the
+// arrivals (grid x passes x ngroups), word 32 the workgroups whose wait ran
+// out (they stop waiting, results do not change), word 64 the longest wait
+// in ticks of strip_wall_khz(). Null: no waits. Two dispatches with one
+// pace buffer running at once (two streams) would share the counter: they
+// would pace wrongly, within the same bounds and with correct results; use
+// one buffer per stream. -1 = rank outside {16,32,64}, nother outside 2..3,
+// a negative budget or a stream not aligned to 128 B; -2 = the tile,
 // tile_rows * (rank + 2) * 8 bytes, exceeds the device's LDS limit.
 template <typename VS>
 int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
@@ -125,12 +135,15 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
                  const int32_t * s_row0, const int32_t * s_nrows,
                  const int32_t * s_flags, const int64_t * s_bounds,
                  int ngroups, int64_t nstrips, int tile_rows, int wgs,
-                 double * out, int rank, int nother, void * stream);
+                 int64_t nnz, double * out, int rank, int nother,
+                 void * stream, uint32_t * pace, int pace_us);
 // Workgroups of that kernel instance resident at once on the current device
 // (occupancy x compute units): the default `wgs`. 0 when the instance does
 // not exist or the tile does not fit. Not for use during stream capture;
 // calling it first also keeps mttkrp_strip free of attribute calls.
 int strip_wgs(int rank, int nother, bool vals32, int tile_rows);
+// Rate of the wall clock that bounds the waits, kHz (0: no device).
+int strip_wall_khz();
 
 // ---------------------------------------------------- mttkrp_det.hip
 // Bitwise-deterministic MTTKRP, V in {double, float}. `out` ([rows, rank],

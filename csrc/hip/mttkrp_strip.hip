@@ -35,16 +35,27 @@
 // advances through the buckets together (2048 nonzeros per round at rank
 // 16).
 //
-// Launches: the strips run in passes of `wgs` workgroups, and a pass in
-// `ngroups` launches, launch g walking the g-th group of windows of every
-// strip of the pass (bounds[s][g] .. bounds[s][g + 1]). Workgroups drift
-// apart by far more than the time one of them spends in a window (measured,
-// profiles/amazon_strip_window.md), so inside one long launch they do not
-// share a window; the launch boundary is the synchronisation that keeps the
-// workgroups of a pass within one group of windows. The tile lives for one
-// launch: launch 0 stores it, later ones add it to the rows with a plain
-// read-modify-write (a strip's unshared rows belong to one workgroup, and
-// the in-order stream orders the launches).
+// One launch per dispatch: the grid is min(wgs, nstrips) workgroups, and
+// workgroup b takes the strips b, b + grid, b + 2 grid, ... (the passes). A
+// strip's windows are cut into `ngroups` groups (bounds[s][g] ..
+// bounds[s][g + 1]); the tile is zeroed once, the groups are walked in order
+// and the tile is stored once. Workgroups left alone drift apart by far more
+// than the time one of them spends in a window (profiles/
+// amazon_strip_window.md), so they would not share a window; after each
+// group every workgroup therefore passes pace(), a counter barrier over the
+// grid, which keeps the workgroups of a pass within one group of windows.
+//
+// pace() carries no data: a strip's tile and unshared rows belong to one
+// workgroup and shared rows are added atomically, so a workgroup that stops
+// waiting loses L2 hits and nothing else. That is what bounds every wait.
+// One lane adds 1 to the arrival counter (relaxed, agent scope) and polls it
+// with relaxed loads and s_sleep until it reaches ticket x grid or the
+// wall-clock budget runs out; on expiry it counts a time-out and the
+// workgroup stops waiting for the rest of the launch, but goes on arriving,
+// so that the others' targets stay reachable. A grid that is not co-resident
+// therefore costs one budget per workgroup, never a hang. Every workgroup
+// makes exactly passes x ngroups calls, also one with no strip in the last
+// pass. Without a pace buffer there are no waits: one unpaced launch.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -77,12 +88,21 @@ struct StripArgs {
   const int32_t * row0, * nrows, * flags;
   const int64_t * bounds;      // [nstrips][ngroups + 1] stream positions
   int ngroups;
+  int64_t nnz;                 // length of the streams
+  uint32_t * pace;             // PACE_* words, zeroed per launch; or null
+  int64_t budget;              // longest wait, in wall_clock64() ticks
 };
+
+// words of the pace buffer, each on a 128-B line of its own
+constexpr int PACE_ARRIVALS = 0;      // pace() calls, all workgroups
+constexpr int PACE_TIMEOUTS = 32;     // workgroups that stopped waiting
+constexpr int PACE_LONGEST = 64;      // longest wait, wall_clock64() ticks
+constexpr int PACE_WORDS = 96;
 
 template <int F, int NOTHER, typename VS>
 __global__ void __launch_bounds__(STRIP_THREADS)
 mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
-                  int64_t strip0, int grp, int tile_rows,
+                  int64_t nstrips, int tile_rows,
                   double * __restrict__ out) {
   constexpr int R = WAVE / F;
   constexpr int W = 32;                          // stream window (nnz)
@@ -102,116 +122,169 @@ mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
   const double * __restrict__ m1 = a.m1;
   const double * __restrict__ m2 = a.m2;
 
-  const int64_t s = strip0 + blockIdx.x;
-  const int32_t row0 = a.row0[s];
-  const int nr = a.nrows[s] < tile_rows ? a.nrows[s] : tile_rows;
-  const int fl = a.flags[s];
-  const int64_t * bnd = a.bounds + s * (a.ngroups + 1) + grp;
-  const int64_t p0 = bnd[0], p1 = bnd[1];
-
-  for (int e = threadIdx.x; e < nr * LD; e += blockDim.x) tile[e] = 0.0;
-  __syncthreads();
+  // the grid barrier after a group of windows; state of the polling lane
+  uint32_t ticket = 0;
+  bool waiting = true;
+  int64_t longest = 0;
+  auto pace = [&]() {
+    if (!a.pace) return;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t * arrivals = a.pace + PACE_ARRIVALS;
+      __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t target = ++ticket * gridDim.x;
+      if (waiting) {
+        const int64_t t0 = (int64_t)wall_clock64();
+        while (__hip_atomic_load(arrivals, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT) < target) {
+          if ((int64_t)wall_clock64() - t0 >= a.budget) {
+            atomicAdd(a.pace + PACE_TIMEOUTS, 1u);
+            waiting = false;     // sticky: no more waits in this launch
+            break;
+          }
+          __builtin_amdgcn_s_sleep(8);
+        }
+        const int64_t dt = (int64_t)wall_clock64() - t0;
+        if (dt > longest) longest = dt;
+      }
+    }
+    __syncthreads();
+  };
 
   const int lane = threadIdx.x & (WAVE - 1);
   const int c = lane % F;
   const int g = lane / F;
   const int gbase = g * F;
   const int slot = c & (W / EPL - 1);            // F=64: lanes 32.. mirror
-  const int ngroups = (blockDim.x / WAVE) * R;
+  const int nlg = (blockDim.x / WAVE) * R;      // lane groups
   const int gid = (threadIdx.x / WAVE) * R + g;
 
-  int32_t cur = -1;
-  double acc = 0.0;
-  // a row outside the strip (a stream that does not match its descriptors)
-  // is dropped, never written past the tile
-  auto flush = [&]() {
-    const uint32_t lr = (uint32_t)(cur - row0);
-    if (lr < (uint32_t)nr) unsafeAtomicAdd(&tile[lr * LD + c], acc);
-  };
-  auto fold = [&](int32_t k, double x) {
-    if (k != cur) {
-      flush();
-      acc = 0.0;
-      cur = k;
+  for (int64_t s = blockIdx.x; s - blockIdx.x < nstrips; s += gridDim.x) {
+    if (s >= nstrips) {          // no strip in the last pass: keep the count
+      for (int grp = 0; grp < a.ngroups; ++grp) pace();
+      break;
     }
-    acc += x;
-  };
-  // one element at a time, every lane of the group reading the same words
-  auto scalar = [&](int64_t pa, int64_t pb) {
-    for (int64_t p = pa; p < pb; ++p) {
-      double x = (double)ldnt(&vals[p]) * m0[(int64_t)ldnt(&i0[p]) * F + c]
-                 * ldnt(&m1[(int64_t)ldnt(&i1[p]) * F + c]);
-      if constexpr (NOTHER > 2)
-        x *= ldnt(&m2[(int64_t)ldnt(&i2[p]) * F + c]);
-      fold(ldnt(&key[p]), x);
-    }
-  };
+    const int32_t row0 = a.row0[s];
+    const int nr = a.nrows[s] < tile_rows ? a.nrows[s] : tile_rows;
+    const int fl = a.flags[s];
+    const int64_t * bnd = a.bounds + s * (a.ngroups + 1);
 
-  // windows are the 128-B lines of the streams (all 128-B aligned): whole
-  // windows [wa, wb) of the strip go round-robin over the groups, the
-  // partial ones at its two ends to the first and the last group
-  const int64_t wa = (p0 + W - 1) / W, wb = p1 / W;
-  const int64_t he = min64(p1, wa * W);
-  const int64_t ts = he > wb * W ? he : wb * W;
-  if (gid == 0) scalar(p0, he);
+    for (int e = threadIdx.x; e < nr * LD; e += blockDim.x) tile[e] = 0.0;
+    __syncthreads();
 
-  for (int64_t w = wa + gid; w < wb; w += ngroups) {
-    const int64_t pw = w * W;
-    const int64_t ps = pw + slot * EPL;
-    int32_t kreg[EPL], i0reg[EPL], i1reg[EPL], i2reg[EPL];
-    VS vreg[NVL][VPL];
-    ldnt_vec(key + ps, kreg);
-    ldnt_vec(i0 + ps, i0reg);
-    ldnt_vec(i1 + ps, i1reg);
-    if constexpr (NOTHER > 2) ldnt_vec(i2 + ps, i2reg);
-    #pragma unroll
-    for (int k = 0; k < NVL; ++k)
-      ldnt_vec(vals + pw + k * CH + slot * VPL, vreg[k]);
-    #pragma unroll
-    for (int k = 0; k < NVL; ++k) {
-      #pragma unroll 1
-      for (int h = 0; h < CH; h += GB) {
-        const int ub = k * CH + h;
-        double vv[GB], a0[GB], a1[GB], a2[GB];
+    int32_t cur = -1;
+    double acc = 0.0;
+    // a row outside the strip (a stream that does not match its descriptors)
+    // is dropped, never written past the tile
+    auto flush = [&]() {
+      const uint32_t lr = (uint32_t)(cur - row0);
+      if (lr < (uint32_t)nr) unsafeAtomicAdd(&tile[lr * LD + c], acc);
+    };
+    auto fold = [&](int32_t k, double x) {
+      if (k != cur) {
+        flush();
+        acc = 0.0;
+        cur = k;
+      }
+      acc += x;
+    };
+    // one element at a time, every lane of the group reading the same words
+    // (the last line of the stream only)
+    auto scalar = [&](int64_t pa, int64_t pb) {
+      for (int64_t p = pa; p < pb; ++p) {
+        double x = (double)ldnt(&vals[p]) * m0[(int64_t)ldnt(&i0[p]) * F + c]
+                   * ldnt(&m1[(int64_t)ldnt(&i1[p]) * F + c]);
+        if constexpr (NOTHER > 2)
+          x *= ldnt(&m2[(int64_t)ldnt(&i2[p]) * F + c]);
+        fold(ldnt(&key[p]), x);
+      }
+    };
+
+    for (int grp = 0; grp < a.ngroups; ++grp) {
+      const int64_t p0 = bnd[grp], p1 = bnd[grp + 1];
+      // windows are the 128-B lines of the streams (all 128-B aligned): the
+      // lines that overlap [p0, p1) go round-robin over the lane groups. A
+      // line cut by p0 or p1 is staged and gathered whole (its other
+      // elements belong to a neighbouring group or strip, so their indices
+      // are valid rows) and only its elements inside the range are folded:
+      // one lane group walking them one by one would hold every workgroup
+      // of the launch at the next pace(). A lane's open run (cur, acc)
+      // carries over into the next group.
+      const int64_t wlo = p0 / W;
+      const int64_t wend = p1 > p0 ? (p1 + W - 1) / W : wlo;
+      // the stream's last line, if it is not a whole one, is not staged
+      const int64_t whi = min64(wend, a.nnz / W);
+
+      for (int64_t w = wlo + gid; w < whi; w += nlg) {
+        const int64_t pw = w * W;
+        // elements [lo, hi) of the line are the group's
+        const int lo = pw < p0 ? (int)(p0 - pw) : 0;
+        const int hi = pw + W > p1 ? (int)(p1 - pw) : W;
+        const int64_t ps = pw + slot * EPL;
+        int32_t kreg[EPL], i0reg[EPL], i1reg[EPL], i2reg[EPL];
+        VS vreg[NVL][VPL];
+        ldnt_vec(key + ps, kreg);
+        ldnt_vec(i0 + ps, i0reg);
+        ldnt_vec(i1 + ps, i1reg);
+        if constexpr (NOTHER > 2) ldnt_vec(i2 + ps, i2reg);
         #pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int src = gbase + ub / EPL + u / EPL;
-          vv[u] = (double)__shfl(vreg[k][u % VPL], gbase + h / VPL + u / VPL,
-                                 WAVE);
-          const int32_t j0 = __shfl(i0reg[u % EPL], src, WAVE);
-          const int32_t j1 = __shfl(i1reg[u % EPL], src, WAVE);
-          a0[u] = m0[(int64_t)j0 * F + c];
-          a1[u] = ldnt(&m1[(int64_t)j1 * F + c]);
-          if constexpr (NOTHER > 2) {
-            const int32_t j2 = __shfl(i2reg[u % EPL], src, WAVE);
-            a2[u] = ldnt(&m2[(int64_t)j2 * F + c]);
+        for (int k = 0; k < NVL; ++k)
+          ldnt_vec(vals + pw + k * CH + slot * VPL, vreg[k]);
+        #pragma unroll
+        for (int k = 0; k < NVL; ++k) {
+          #pragma unroll 1
+          for (int h = 0; h < CH; h += GB) {
+            const int ub = k * CH + h;
+            double vv[GB], a0[GB], a1[GB], a2[GB];
+            #pragma unroll
+            for (int u = 0; u < GB; ++u) {
+              const int src = gbase + ub / EPL + u / EPL;
+              vv[u] = (double)__shfl(vreg[k][u % VPL],
+                                     gbase + h / VPL + u / VPL, WAVE);
+              const int32_t j0 = __shfl(i0reg[u % EPL], src, WAVE);
+              const int32_t j1 = __shfl(i1reg[u % EPL], src, WAVE);
+              a0[u] = m0[(int64_t)j0 * F + c];
+              a1[u] = ldnt(&m1[(int64_t)j1 * F + c]);
+              if constexpr (NOTHER > 2) {
+                const int32_t j2 = __shfl(i2reg[u % EPL], src, WAVE);
+                a2[u] = ldnt(&m2[(int64_t)j2 * F + c]);
+              }
+            }
+            #pragma unroll
+            for (int u = 0; u < GB; ++u) {
+              double x = vv[u] * a0[u] * a1[u];
+              if constexpr (NOTHER > 2) x *= a2[u];
+              const int32_t k = __shfl(kreg[u % EPL],
+                                       gbase + ub / EPL + u / EPL, WAVE);
+              if (ub + u >= lo && ub + u < hi) fold(k, x);
+            }
           }
         }
-        #pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          double x = vv[u] * a0[u] * a1[u];
-          if constexpr (NOTHER > 2) x *= a2[u];
-          fold(__shfl(kreg[u % EPL], gbase + ub / EPL + u / EPL, WAVE), x);
-        }
       }
+
+      if (wend > whi && gid == nlg - 1)
+        scalar(whi * W > p0 ? whi * W : p0, p1);
+      if (grp + 1 < a.ngroups) pace();
     }
-  }
+    flush();
+    __syncthreads();
 
-  if (gid == ngroups - 1) scalar(ts, p1);
-  flush();
-  __syncthreads();
-
-  for (int e = threadIdx.x; e < nr * F; e += blockDim.x) {
-    const int lr = e / F, cc = e % F;
-    const double v = tile[lr * LD + cc];
-    double * o = &out[(int64_t)(row0 + lr) * F + cc];
-    if ((lr == 0 && (fl & 1)) || (lr == nr - 1 && (fl & 2)))
-      atomic_add_g(o, v);
-    else if (grp == 0)
-      *o = v;
-    else
-      *o += v;             // the strip's rows are this workgroup's alone
+    for (int e = threadIdx.x; e < nr * F; e += blockDim.x) {
+      const int lr = e / F, cc = e % F;
+      const double v = tile[lr * LD + cc];
+      double * o = &out[(int64_t)(row0 + lr) * F + cc];
+      if ((lr == 0 && (fl & 1)) || (lr == nr - 1 && (fl & 2)))
+        atomic_add_g(o, v);
+      else
+        *o = v;                // the strip's other rows are this workgroup's
+    }
+    // the stores of the fast workgroups overlap the walk of the slow ones
+    if (a.pace) pace(); else __syncthreads();
   }
+  if (a.pace && threadIdx.x == 0 && longest > 0)
+    atomicMax(a.pace + PACE_LONGEST,
+              (uint32_t)(longest < 0xFFFFFFFFll ? longest : 0xFFFFFFFFll));
 }
 
 // largest dynamic LDS request a block may make on the current device
@@ -241,6 +314,20 @@ inline int cu_count() {
   return n;
 }
 
+// wall_clock64() ticks per millisecond (the constant-rate clock of pace())
+inline int wall_khz() {
+  static int khz = -1;
+  if (khz < 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess
+        || hipDeviceGetAttribute(&v, hipDeviceAttributeWallClockRate, dev)
+               != hipSuccess || v <= 0)
+      return 0;
+    khz = v;
+  }
+  return khz;
+}
+
 struct StripLaunch {
   StripArgs a;
   const void * vals;
@@ -253,7 +340,7 @@ struct StripLaunch {
 
 // One kernel instance: raise its dynamic-LDS limit to `lds` bytes (once per
 // size), then either answer the resident-workgroup count (L == nullptr) or
-// launch the passes.
+// clear the pace words and launch the grid.
 template <int F, int NOTHER, typename VS>
 int strip_inst(const StripLaunch * L, int lds, int * wgs) {
   static int lds_set = 0;
@@ -271,16 +358,19 @@ int strip_inst(const StripLaunch * L, int lds, int * wgs) {
         &per_cu, kern, STRIP_THREADS, (size_t)lds);
     if (e != hipSuccess) return (int)e;
     *wgs = per_cu * cu_count();
-    return 0;
+    return wall_khz() > 0 ? 0 : (int)hipErrorInvalidDevice;
   }
-  for (int64_t s0 = 0; s0 < L->nstrips; s0 += L->wgs) {
-    const int64_t n = L->nstrips - s0 < L->wgs ? L->nstrips - s0 : L->wgs;
-    for (int g = 0; g < L->a.ngroups; ++g)
-      hipLaunchKernelGGL(kern, dim3((uint32_t)n), dim3(STRIP_THREADS),
-                         (size_t)lds, L->st, L->a,
-                         static_cast<const VS *>(L->vals), s0, g,
-                         L->tile_rows, L->out);
+  if (L->a.pace) {
+    // a memset node under capture: a replay starts from zero as well
+    const hipError_t e = hipMemsetAsync(
+        L->a.pace, 0, PACE_WORDS * sizeof(uint32_t), L->st);
+    if (e != hipSuccess) return (int)e;
   }
+  const int64_t n = L->nstrips < L->wgs ? L->nstrips : L->wgs;
+  hipLaunchKernelGGL(kern, dim3((uint32_t)n), dim3(STRIP_THREADS),
+                     (size_t)lds, L->st, L->a,
+                     static_cast<const VS *>(L->vals), L->nstrips,
+                     L->tile_rows, L->out);
   return launch_rc();
 }
 
@@ -321,16 +411,19 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
                  const int32_t * s_row0, const int32_t * s_nrows,
                  const int32_t * s_flags, const int64_t * s_bounds,
                  int ngroups, int64_t nstrips, int tile_rows, int wgs,
-                 double * out, int rank, int nother, void * stream) {
+                 int64_t nnz, double * out, int rank, int nother,
+                 void * stream, uint32_t * pace, int pace_us) {
   if (nstrips <= 0) return 0;
-  if (wgs < 1 || ngroups < 1 || nother < 2 || nother > 3) return -1;
+  if (wgs < 1 || ngroups < 1 || nother < 2 || nother > 3 || pace_us < 0)
+    return -1;
   // windows are the streams' 128-B lines
   uintptr_t bits = (uintptr_t)key | (uintptr_t)vals;
   for (int t = 0; t < nother; ++t) bits |= (uintptr_t)idx[t];
   if (bits & 127) return -1;
   StripLaunch L{{key, idx[0], idx[1], nother > 2 ? idx[2] : nullptr, mats[0],
                  mats[1], nother > 2 ? mats[2] : nullptr, s_row0, s_nrows,
-                 s_flags, s_bounds, ngroups},
+                 s_flags, s_bounds, ngroups, nnz, pace,
+                 (int64_t)pace_us * wall_khz() / 1000},
                 vals, nstrips, wgs, tile_rows, out, (hipStream_t)stream};
   return strip_dispatch<VS>(&L, tile_rows, rank, nother, nullptr);
 }
@@ -338,10 +431,13 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
 #define STRIP_SIG(VS)                                                      \
   const int32_t *, const int32_t * const *, const double * const *,        \
   const VS *, const int32_t *, const int32_t *, const int32_t *,           \
-  const int64_t *, int, int64_t, int, int, double *, int, int, void *
+  const int64_t *, int, int64_t, int, int, int64_t, double *, int, int,    \
+  void *, uint32_t *, int
 template int mttkrp_strip<double>(STRIP_SIG(double));
 template int mttkrp_strip<float>(STRIP_SIG(float));
 #undef STRIP_SIG
+
+int strip_wall_khz() { return wall_khz(); }
 
 }  // namespace hip
 }  // namespace splatt

@@ -580,12 +580,14 @@ static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
 // descriptors of splatt_amd/csf.py (device arrays), f64 or f32 value stream,
 // f64 factors and output. Returns false when the launcher declines
 // (misaligned streams, tile above the LDS limit) — the caller then takes the
-// key-stream kernel.
+// key-stream kernel. `pace` (96 words of uint32 or int32, or None: no
+// waits) and `pace_us` are the pace buffer and wait budget of launchers.hpp.
 static bool py_mttkrp_strip_gpu(Tensor key, std::vector<Tensor> idx,
                                 std::vector<Tensor> mats, Tensor vals,
                                 Tensor s_row0, Tensor s_nrows, Tensor s_flags,
                                 Tensor s_bounds, int64_t tile_rows,
-                                int64_t wgs, Tensor out, int64_t stream) {
+                                int64_t wgs, Tensor out, int64_t stream,
+                                c10::optional<Tensor> pace, int64_t pace_us) {
   const size_t nother = idx.size();
   TORCH_CHECK(nother >= 2 && nother <= 3, "strip kernel supports 3..4 modes");
   TORCH_CHECK(tile_rows >= 1 && tile_rows <= (1 << 20) && wgs >= 1
@@ -607,15 +609,30 @@ static bool py_mttkrp_strip_gpu(Tensor key, std::vector<Tensor> idx,
               && s_bounds.size(1) >= 2 && s_bounds.size(1) <= (1 << 16),
               "strip descriptor lengths differ");
   const int ng = (int)s_bounds.size(1) - 1;
+  uint32_t * pp = nullptr;
+  if (pace.has_value()) {
+    const Tensor & p = *pace;
+    TORCH_CHECK(p.is_cuda(), "pace must be a device tensor");
+    TORCH_CHECK(p.scalar_type() == torch::kInt32
+                || p.scalar_type() == at::ScalarType::UInt32,
+                "pace has dtype ", p.scalar_type(), ", expected Int or UInt32");
+    TORCH_CHECK(p.is_contiguous() && p.numel() >= 96,
+                "pace must be contiguous and hold at least 96 words");
+    pp = static_cast<uint32_t *>(p.data_ptr());
+  }
+  TORCH_CHECK(pace_us >= 0 && pace_us <= 60 * 1000 * 1000,
+              "pace_us out of range");
   const int rc = vals.scalar_type() == torch::kFloat32
       ? gpu::mttkrp_strip<float>(kp, ip.data(), mp.data(),
                                  dev_ptr<float>(vals, "vals"), r0, nr, fl, bp,
-                                 ng, ns, (int)tile_rows, (int)wgs, op, rank,
-                                 (int)nother, (void *)stream)
+                                 ng, ns, (int)tile_rows, (int)wgs, nnz, op,
+                                 rank, (int)nother, (void *)stream, pp,
+                                 (int)pace_us)
       : gpu::mttkrp_strip<double>(kp, ip.data(), mp.data(),
                                   dev_ptr<double>(vals, "vals"), r0, nr, fl,
-                                  bp, ng, ns, (int)tile_rows, (int)wgs, op,
-                                  rank, (int)nother, (void *)stream);
+                                  bp, ng, ns, (int)tile_rows, (int)wgs, nnz,
+                                  op, rank, (int)nother, (void *)stream, pp,
+                                  (int)pace_us);
   if (rc > 0) check_rc(rc, "strip MTTKRP");
   return rc == 0;
 }
@@ -1147,7 +1164,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "row pointers or key stream; false = declined, use the f64 stream");
   m.def("mttkrp_strip_gpu", &py_mttkrp_strip_gpu,
         "strip/window flat MTTKRP (root output in LDS tiles over a "
-        "strip-layout stream); false = declined, use gpu_mttkrp_flat");
+        "strip-layout stream); false = declined, use gpu_mttkrp_flat",
+        py::arg("key"), py::arg("idx"), py::arg("mats"), py::arg("vals"),
+        py::arg("s_row0"), py::arg("s_nrows"), py::arg("s_flags"),
+        py::arg("s_bounds"), py::arg("tile_rows"), py::arg("wgs"),
+        py::arg("out"), py::arg("stream"), py::arg("pace") = py::none(),
+        py::arg("pace_us") = 3600);
+  m.def("strip_wall_khz", &gpu::strip_wall_khz,
+        "rate of the wall clock of the strip kernel's pace words, kHz");
   m.def("strip_wgs", &gpu::strip_wgs,
         "resident workgroups of a strip kernel instance on this device "
         "(rank, nother, f32 values, tile rows); 0 = no such instance");

@@ -242,7 +242,8 @@ def strip_layout(root: torch.Tensor, widx: torch.Tensor, nrows: int,
     (strip, widx // window_rows) — inside a (strip, window) cell the order
     stays (row, remaining levels). strips["bounds"] ([strips, groups + 1])
     cuts every strip's range at the same `groups` + 1 window boundaries:
-    one launch of the kernel walks one group of windows of its strips."""
+    the kernel's workgroups wait for each other after each group of windows
+    of their strips."""
     dev = root.device
     rowptr = torch.searchsorted(
         root.contiguous(),
@@ -289,8 +290,9 @@ def build_csf(t: SpTensor, perm: Sequence[int], flat_only: bool = False,
     says: rows per strip, `strip_cap` nonzeros per strip (0: the mean strip
     load), `strip_window` rows of the window level per window (0: 1 MiB of
     factor rows), `strip_wgs` workgroups per launch (0: what the device
-    holds), `strip_groups` launches per pass, each over one group of
-    windows (0: the default, STRIP_GROUP_KB of factor rows per group)."""
+    holds), `strip_groups` groups of windows per strip, the workgroups of
+    the launch pacing each other from group to group (0: the default,
+    STRIP_GROUP_KB of factor rows per group)."""
     if any(d > 0xFFFFFFFF for d in t.dims):
         raise ValueError("mode dimensions above 2^32 are not supported "
                          "(CSF node ids are 32-bit; shard the mode first)")
@@ -337,9 +339,9 @@ def _strip_wgs(rank: int, nother: int, tile_rows: int) -> int:
                for v32 in (False, True))
 
 
-# factor bytes of the window level per launch group: the workgroups of a
+# factor bytes of the window level per pace group: the workgroups of the
 # launch stay within this much of the factor (measured default,
-# profiles/amazon_strip_window.md); SPLATT_STRIP_GROUP_KB overrides
+# profiles/amazon_strip_paced.md); SPLATT_STRIP_GROUP_KB overrides
 STRIP_GROUP_KB = 16384
 
 
@@ -497,8 +499,8 @@ def _build_csf_device(t: SpTensor, perm: List[int],
                 t.dims[perm[w]] * stage_rank_in * 8))
         order = order.index_select(0, sorder)
         del sorder
-        # launches take the strips in this order: heaviest first, so the
-        # workgroups of one launch carry like loads and finish together
+        # the passes take the strips in this order: heaviest first, so the
+        # workgroups of one pass carry like loads and finish together
         by_load = torch.argsort(strips["p1"] - strips["p0"], descending=True,
                                 stable=True)
         strip_meta = dict(strip_cfg, cap=int(cap),
@@ -506,6 +508,9 @@ def _build_csf_device(t: SpTensor, perm: List[int],
         strip_meta["groups"] = int(strips["bounds"].shape[1]) - 1
         for k in ("row0", "nrows", "flags", "p0", "p1", "bounds"):
             strip_meta[k] = strips[k].index_select(0, by_load).to(dev)
+        # the kernel's pace words (arrivals, time-outs, longest wait; 96
+        # words, csrc/hip/launchers.hpp), cleared by every dispatch
+        strip_meta["pace"] = torch.zeros(96, dtype=torch.int32, device=dev)
     sinds = [t.inds[perm[l]].index_select(0, order) for l in range(nm)]
     svals = t.vals.index_select(0, order)
 

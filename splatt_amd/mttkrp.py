@@ -371,11 +371,15 @@ def _gpu_mttkrp_flat(c: Csf, depth: int, mats: List[torch.Tensor],
             idx = [c.ancestor_expand(l).contiguous() for l in lv]
             ms = [mats[c.dim_perm[l]].contiguous() for l in lv]
             v32 = _vals32(c, rank, mats)
+            # one launch, its workgroups paced group by group through the
+            # CSF's pace words (SPLATT_STRIP_PACE=0: no waits)
+            paced = os.environ.get("SPLATT_STRIP_PACE") != "0"
             if native().mttkrp_strip_gpu(
                     key.contiguous(), idx, ms, c.vals if v32 is None else v32,
                     strip["row0"], strip["nrows"], strip["flags"],
                     strip["bounds"], strip["tile_rows"],
-                    strip["wgs"], out, stream):
+                    strip["wgs"], out, stream,
+                    strip["pace"] if paced else None, _strip_pace_us()):
                 return
     p0, p1 = 0, c.nnz
     if rows is not None:
@@ -415,6 +419,30 @@ def factor_store_dtype():
     (documented mode — the default and every headline number stay f64)."""
     env = os.environ.get("SPLATT_FACTOR_STORE", "")
     return {"f32": torch.float32, "bf16": torch.bfloat16}.get(env)
+
+
+# longest wait of a workgroup at one pace point of the strip kernel, in
+# microseconds: 4x the longest wait of a bench.py run on the Amazon shape
+# (880 us, profiles/amazon_strip_paced.md), since waits grow with the group
+# size and the imbalance of a pass; SPLATT_STRIP_PACE_US overrides
+STRIP_PACE_US = 3600
+
+
+def _strip_pace_us() -> int:
+    return max(0, int(os.environ.get("SPLATT_STRIP_PACE_US",
+                                     str(STRIP_PACE_US))))
+
+
+def strip_pace_stats(c: Csf) -> tuple:
+    """(arrivals, time-outs, longest wait in microseconds) left in the pace
+    words of a strip-layout CSF by its last strip dispatch: arrivals is
+    workgroups x passes x groups, time-outs the workgroups whose wait ran out
+    (they stop waiting; results are unaffected). Synchronises the device, so
+    it is for tests and profiling, not for the step path."""
+    words = c._strip["pace"].cpu().tolist()   # type: ignore[attr-defined]
+    khz = native().strip_wall_khz()
+    return (words[0] & 0xFFFFFFFF, words[32] & 0xFFFFFFFF,
+            (words[64] & 0xFFFFFFFF) * 1000.0 / khz if khz > 0 else 0.0)
 
 
 def mttkrp_rows_ok(src: CsfSet | Csf, mode: int, rank: int) -> bool:
