@@ -44,6 +44,30 @@ inline int64_t pick_span(int64_t nnz) {
   return span;
 }
 
+// Sub-spans of the flat kernels: [p0, p1) is part `sub` of the `nsub` even
+// parts of [lo, hi); false when it is empty. Computed here alone for v2,
+// v5, v6 and the key-sorted deterministic pair, whose fixup re-derives every
+// walker's range and must agree with the kernel it follows. (det6 and its
+// fixup write the same arithmetic out: with this helper their comparisons
+// come out mirrored, and their code is kept instruction-identical.)
+__device__ __forceinline__ bool sub_range(int64_t lo, int64_t hi, int sub,
+                                          int nsub, int64_t & p0,
+                                          int64_t & p1) {
+  const int64_t gsz = (hi - lo + nsub - 1) / nsub;
+  p0 = min64(hi, lo + sub * gsz);
+  p1 = min64(hi, p0 + gsz);
+  return p0 < p1;
+}
+
+// ... of column group g (of R) of wave wid, which covers [wid*span, ..)
+__device__ __forceinline__ bool group_range(int64_t wid, int g, int R,
+                                            int64_t nnz, int64_t span,
+                                            int64_t & p0, int64_t & p1) {
+  const int64_t w0 = wid * span;
+  if (w0 >= nnz) return false;
+  return sub_range(w0, min64(nnz, w0 + span), g, R, p0, p1);
+}
+
 // status of the launches just made, in the launcher return convention
 // (launchers.hpp): 0 or a positive hipError_t
 inline int launch_rc() { return (int)hipGetLastError(); }

@@ -64,8 +64,8 @@ int mttkrp_csf3(int which, const int64_t * fptr0, const int32_t * fids0,
 //   rowptr  root output of a key-sorted stream: int64, nrows + 1 GLOBAL
 //           stream positions; p0 is the global position of the launch's
 //           first nonzero, i.e. idx/vals point at element p0. v7 only.
-// v7 declines (-1) for a rank outside {8,16,32,64}, nother > 4, a set
-// SPLATT_MTTKRP_U lever, streams that are not co-aligned to 128 B, and
+// v7 declines (-1) for a rank outside {8,16,32,64}, nother > 4,
+// SPLATT_MTTKRP_U=1, streams that are not co-aligned to 128 B, and
 // rank 8 / 3 modes with 8-byte values and factors.
 template <typename V, typename S = V, typename VS = V>
 int mttkrp_flat(const int32_t * key, const int64_t * rowptr, int64_t nrows,

@@ -36,23 +36,10 @@
 
 namespace {
 
-// walker -> its contiguous nnz range (the flat-v2 span decomposition:
-// wave `wid` covers [wid*span, ..), split into R = WAVE/F group spans)
-__device__ __forceinline__ bool walker_range(int64_t w, int64_t nnz,
-                                             int64_t span, int R,
-                                             int64_t & p0, int64_t & p1) {
-  const int64_t wid = w / R;
-  const int g = (int)(w % R);
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return false;
-  const int64_t w1 = min64(nnz, w0 + span);
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  p0 = min64(w1, w0 + (int64_t)g * gsz);
-  p1 = min64(w1, p0 + gsz);
-  return p0 < p1;
-}
-
-template <typename V, int F, int NOTHER, int GBP = 8>
+// A walker is a column group of the flat-v2 span decomposition: walker w is
+// group w % R of wave w / R, and group_range (device_common.hpp) gives its
+// contiguous nnz range to the kernel and to the fixup alike.
+template <typename V, int F, int NOTHER>
 __global__ void __launch_bounds__(256)
 mttkrp_det_kern(const int32_t * __restrict__ key,
                 const int32_t * __restrict__ i0,
@@ -64,20 +51,15 @@ mttkrp_det_kern(const int32_t * __restrict__ key,
                 const V * __restrict__ vals, int64_t nnz, int64_t span,
                 V * __restrict__ out, V * __restrict__ side) {
   constexpr int R = WAVE / F;
-  constexpr int GB = (F >= GBP) ? GBP : F;
+  constexpr int GB = (F >= 8) ? 8 : F;
   const int lane = threadIdx.x & (WAVE - 1);
   const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
                       + (threadIdx.x / WAVE);
   const int c = lane % F;
   const int g = lane / F;
   const int gbase = g * F;
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return;
-  const int64_t w1 = min64(nnz, w0 + span);
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  const int64_t p0 = min64(w1, w0 + g * gsz);
-  const int64_t p1 = min64(w1, p0 + gsz);
-  if (p0 >= p1) return;
+  int64_t p0, p1;
+  if (!group_range(wid, g, R, nnz, span, p0, p1)) return;
 
   const int64_t wkr = wid * R + g;          // global walker id
   const int32_t kf = key[p0];
@@ -152,7 +134,7 @@ mttkrp_det_fixup_kern(const int32_t * __restrict__ key, int64_t nnz,
   const int c = threadIdx.x % F;
   if (w >= nwalkers) return;
   int64_t p0, p1;
-  if (!walker_range(w, nnz, span, R, p0, p1)) return;
+  if (!group_range(w / R, (int)(w % R), R, nnz, span, p0, p1)) return;
   const int32_t kf = key[p0];
   const int32_t kl = key[p1 - 1];
 
@@ -160,7 +142,7 @@ mttkrp_det_fixup_kern(const int32_t * __restrict__ key, int64_t nnz,
     V tot = (V)0;
     for (int64_t x = w; x < nwalkers; ++x) {
       int64_t q0, q1;
-      if (!walker_range(x, nnz, span, R, q0, q1)) continue;
+      if (!group_range(x / R, (int)(x % R), R, nnz, span, q0, q1)) continue;
       const int32_t xf = key[q0];
       if (xf > k) break;
       const int32_t xl = key[q1 - 1];

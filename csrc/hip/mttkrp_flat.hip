@@ -11,7 +11,7 @@
 // `key` is piecewise-constant, so each 64/F-lane column group walks a
 // contiguous sub-span serially, folds products into a register accumulator,
 // and emits one hardware f64/f32 atomic-add per key RUN — not per nonzero.
-// The U-deep unrolled loads are independent, so the loop is
+// The factor-row gathers of a batch are independent, so the loop is
 // throughput-bound, not latency-bound (the CSF-walk family in
 // mttkrp_kernels.hip is kept as a comparison algorithm, reference-style
 // `splatt bench -a`).
@@ -33,92 +33,16 @@ namespace {
 using splatt_store::bf16;
 using splatt_store::to_compute;
 
-// ---------------------------------------------------------- spec kernels
-// F lanes per column group, R = 64/F groups each walking a contiguous
-// sub-span; U-deep unroll for memory-level parallelism.
-template <typename V, int F, int NOTHER, int U = 8>
-__global__ void __launch_bounds__(256)
-mttkrp_flat_kern(const int32_t * __restrict__ key,
-                 const int32_t * __restrict__ i0,
-                 const int32_t * __restrict__ i1,
-                 const int32_t * __restrict__ i2,
-                 const int32_t * __restrict__ i3,
-                 const V * __restrict__ m0, const V * __restrict__ m1,
-                 const V * __restrict__ m2, const V * __restrict__ m3,
-                 const V * __restrict__ vals, int64_t nnz, int64_t span,
-                 V * __restrict__ out) {
-  constexpr int R = WAVE / F;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
-                      + (threadIdx.x / WAVE);
-  const int c = lane % F;
-  const int g = lane / F;
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return;
-  const int64_t w1 = min64(nnz, w0 + span);
-  // contiguous sub-span per column group
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  const int64_t p0 = min64(w1, w0 + g * gsz);
-  const int64_t p1 = min64(w1, p0 + gsz);
-  if (p0 >= p1) return;
-
-  int32_t cur = key[p0];
-  V acc = (V)0;
-  int64_t p = p0;
-  while (p < p1) {
-    const int n = (int)min64((int64_t)U, p1 - p);
-    int32_t k[U];
-    V prod[U];
-    if (n == U) {
-      #pragma unroll
-      for (int u = 0; u < U; ++u) k[u] = ldnt(&key[p + u]);
-      #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        V x = ldnt(&vals[p + u]) * m0[(int64_t)ldnt(&i0[p + u]) * F + c]
-                          * m1[(int64_t)ldnt(&i1[p + u]) * F + c];
-        if (NOTHER > 2) x *= m2[(int64_t)ldnt(&i2[p + u]) * F + c];
-        if (NOTHER > 3) x *= m3[(int64_t)ldnt(&i3[p + u]) * F + c];
-        prod[u] = x;
-      }
-    } else {
-      #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (u < n) {
-          k[u] = ldnt(&key[p + u]);
-          V x = ldnt(&vals[p + u]) * m0[(int64_t)ldnt(&i0[p + u]) * F + c]
-                            * m1[(int64_t)ldnt(&i1[p + u]) * F + c];
-          if (NOTHER > 2) x *= m2[(int64_t)ldnt(&i2[p + u]) * F + c];
-          if (NOTHER > 3) x *= m3[(int64_t)ldnt(&i3[p + u]) * F + c];
-          prod[u] = x;
-        } else {
-          k[u] = cur;        // no-op in the fold
-          prod[u] = (V)0;
-        }
-      }
-    }
-    #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (k[u] != cur) {     // rare for root output; per-run for intl/leaf
-        atomic_add_g(&out[(int64_t)cur * F + c], acc);
-        acc = (V)0;
-        cur = k[u];
-      }
-      acc += prod[u];
-    }
-    p += n;
-  }
-  atomic_add_g(&out[(int64_t)cur * F + c], acc);
-}
-
 // ------------------------------------------------- staged spec kernel (v2)
-// v1 has every lane of a column group redundantly load the same stream
-// words (key/idx/vals), so memory-level parallelism is capped by the VGPR
-// cost of the unroll. v2 stages streams COALESCED — lane slot c of a group
-// loads element pb+c of each stream in one instruction per F nonzeros —
-// and redistributes them with ds_bpermute (__shfl); the factor-row gathers
-// then issue in independent batches of 8, giving ~4x the outstanding
-// gathers per wave at lower VGPR pressure.
-template <typename V, int F, int NOTHER, int GBP = 8, typename S = V>
+// F lanes per column group, R = 64/F groups each walking a contiguous
+// sub-span. Having every lane of a group load the same stream words
+// (key/idx/vals) caps memory-level parallelism by the VGPR cost of the
+// unroll (the retired v1, docs/KERNELS.md). v2 stages streams COALESCED —
+// lane slot c of a group loads element pb+c of each stream in one
+// instruction per F nonzeros — and redistributes them with ds_bpermute
+// (__shfl); the factor-row gathers then issue in independent batches of 8,
+// giving ~4x the outstanding gathers per wave at lower VGPR pressure.
+template <typename V, int F, int NOTHER, typename S = V>
 __global__ void __launch_bounds__(256)
 mttkrp_flat2_kern(const int32_t * __restrict__ key,
                   const int32_t * __restrict__ i0,
@@ -130,20 +54,15 @@ mttkrp_flat2_kern(const int32_t * __restrict__ key,
                   const V * __restrict__ vals, int64_t nnz, int64_t span,
                   V * __restrict__ out) {
   constexpr int R = WAVE / F;
-  constexpr int GB = (F >= GBP) ? GBP : F;   // gather sub-batch
+  constexpr int GB = (F >= 8) ? 8 : F;       // gather sub-batch
   const int lane = threadIdx.x & (WAVE - 1);
   const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
                       + (threadIdx.x / WAVE);
   const int c = lane % F;
   const int g = lane / F;
   const int gbase = g * F;
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return;
-  const int64_t w1 = min64(nnz, w0 + span);
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  const int64_t p0 = min64(w1, w0 + g * gsz);
-  const int64_t p1 = min64(w1, p0 + gsz);
-  if (p0 >= p1) return;
+  int64_t p0, p1;
+  if (!group_range(wid, g, R, nnz, span, p0, p1)) return;
 
   int32_t cur = key[p0];
   V acc = (V)0;
@@ -402,14 +321,11 @@ mttkrp_flat7_kern(const int32_t * __restrict__ key,
   atomic_add_g(&out[(int64_t)cur * F + c], acc);
 }
 
-inline int pick_unroll() {
-  // A/B lever: 0 (default) = full-line staged v7 kernel (v2 at rank 4 or
-  // when the streams are not co-aligned); 1 = force v2; 2 = v2 with gather
-  // batch 4; 3 = v3; 5 = v4; 4/8/16 = v1 at that unroll
+// A/B lever: SPLATT_MTTKRP_U=1 makes v7 decline, so that v2 runs in its
+// place (the same-binary oracle of the tests). Any other value is as unset.
+inline bool force_v2() {
   const char * e = getenv("SPLATT_MTTKRP_U");
-  const int u = e ? atoi(e) : 0;
-  return (u == 1 || u == 2 || u == 3 || u == 4 || u == 5 || u == 8
-          || u == 16) ? u : 0;
+  return e && atoi(e) == 1;
 }
 
 // Elements between the preceding 128-B line boundary of the int32 streams
@@ -429,9 +345,9 @@ inline int stream_phase(const int32_t * key, const int32_t * const idx[8],
 
 // v7 launcher; rowptr != nullptr selects the row-pointer variant (key may
 // then be null). Returns false, launching nothing, when v7 does not apply:
-// rank outside 8/16/32/64, more than 4 other modes, an SPLATT_MTTKRP_U
-// lever set, streams that are not co-aligned, or the one instance that
-// would lose occupancy (below).
+// rank outside 8/16/32/64, more than 4 other modes, SPLATT_MTTKRP_U=1,
+// streams that are not co-aligned, or the one instance that would lose
+// occupancy (below).
 // span is pick_span() rounded DOWN to a multiple of 32*R (R = 64/F groups
 // per wave: 256/128/64/32 at F = 8/16/32/64) so that every group's sub-span
 // is a whole number of 32-element windows. The 256 minimum and the 16384
@@ -442,7 +358,7 @@ bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
                   const S * const mats[8], const VS * vals, int64_t nnz,
                   V * out, int rank, int nother, hipStream_t st) {
   if (!(rank == 8 || rank == 16 || rank == 32 || rank == 64)) return false;
-  if (nother < 2 || nother > 4 || pick_unroll() != 0) return false;
+  if (nother < 2 || nother > 4 || force_v2()) return false;
   // the one instance whose 16-B staging costs occupancy: rank 8, 3 modes,
   // f64 values and factors needs 102 (row pointers) / 106 (key) VGPRs
   // against v2's 95, i.e. 4 waves/SIMD instead of 5, and forcing 5 spills
@@ -479,235 +395,6 @@ bool launch_flat7(const int32_t * key, const int64_t * rowptr, int64_t nrows,
 #undef L7
 #undef ARGS7
   return true;
-}
-
-// storage-typed launcher (reduced-precision factor STORE for non-staged
-// HBM-bound dispatches) for what v7 declines: v2
-template <typename V, typename S>
-void launch_flat_store(const int32_t * key, const int32_t * const idx[8],
-                       const S * const mats[8], const V * vals, int64_t nnz,
-                       V * out, int rank, int nother, hipStream_t st) {
-  const int64_t span = pick_span(nnz);
-  const int64_t nwaves = (nnz + span - 1) / span;
-  const int wpb = 4;
-  const int64_t nblocks = (nwaves + wpb - 1) / wpb;
-  dim3 grid((uint32_t)nblocks), block(wpb * WAVE);
-#define SARGS key, idx[0], idx[1], idx[2], idx[3], mats[0], mats[1], \
-              mats[2], mats[3], vals, nnz, span, out
-#define LS(F_, N_) \
-  hipLaunchKernelGGL((mttkrp_flat2_kern<V, F_, N_, 8, S>), grid, block, 0, \
-                     st, SARGS)
-#define LSF(N_) \
-  switch (rank) { case 4: LS(4, N_); break; case 8: LS(8, N_); break; \
-                  case 16: LS(16, N_); break; case 32: LS(32, N_); break; \
-                  default: LS(64, N_); break; }
-  switch (nother) {
-    case 2: LSF(2); break;
-    case 3: LSF(3); break;
-    default: LSF(4); break;
-  }
-#undef LSF
-#undef LS
-#undef SARGS
-}
-
-// ------------------------------------------- pipelined spec kernel (v3)
-// v2 with double-buffered gather batches: batch k+1's factor-row gathers
-// are ISSUED before batch k is folded, so the fold overlaps the next
-// batch's memory latency (hipcc emits counted s_waitcnt instead of a full
-// drain per batch). Costs ~2x the batch registers.
-template <typename V, int F, int NOTHER>
-__global__ void __launch_bounds__(256)
-mttkrp_flat3_kern(const int32_t * __restrict__ key,
-                  const int32_t * __restrict__ i0,
-                  const int32_t * __restrict__ i1,
-                  const int32_t * __restrict__ i2,
-                  const int32_t * __restrict__ i3,
-                  const V * __restrict__ m0, const V * __restrict__ m1,
-                  const V * __restrict__ m2, const V * __restrict__ m3,
-                  const V * __restrict__ vals, int64_t nnz, int64_t span,
-                  V * __restrict__ out) {
-  constexpr int R = WAVE / F;
-  constexpr int GB = (F >= 8) ? 8 : F;
-  constexpr int NB = (F + GB - 1) / GB;   // batches per stream window
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
-                      + (threadIdx.x / WAVE);
-  const int c = lane % F;
-  const int g = lane / F;
-  const int gbase = g * F;
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return;
-  const int64_t w1 = min64(nnz, w0 + span);
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  const int64_t p0 = min64(w1, w0 + g * gsz);
-  const int64_t p1 = min64(w1, p0 + gsz);
-  if (p0 >= p1) return;
-
-  int32_t cur = key[p0];
-  V acc = (V)0;
-  int32_t kk[2][GB];
-  V vv[2][GB], a0[2][GB], a1[2][GB], a2[2][GB], a3[2][GB];
-
-  for (int64_t pb = p0; pb < p1; pb += F) {
-    const int nb = (int)min64((int64_t)F, p1 - pb);
-    const int64_t ps = pb + (c < nb ? c : nb - 1);
-    const int32_t kreg = ldnt(&key[ps]);
-    const int32_t i0reg = ldnt(&i0[ps]);
-    const int32_t i1reg = ldnt(&i1[ps]);
-    const int32_t i2reg = (NOTHER > 2) ? ldnt(&i2[ps]) : 0;
-    const int32_t i3reg = (NOTHER > 3) ? ldnt(&i3[ps]) : 0;
-    const V vreg = ldnt(&vals[ps]);
-
-    auto issue = [&](int buf, int ub, int ne) {
-      #pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        const int src = gbase + (u < ne ? ub + u : ub);
-        kk[buf][u] = __shfl(kreg, src, WAVE);
-        vv[buf][u] = __shfl(vreg, src, WAVE);
-        const int32_t j0 = __shfl(i0reg, src, WAVE);
-        const int32_t j1 = __shfl(i1reg, src, WAVE);
-        a0[buf][u] = m0[(int64_t)j0 * F + c];
-        a1[buf][u] = m1[(int64_t)j1 * F + c];
-        if (NOTHER > 2) {
-          const int32_t j2 = __shfl(i2reg, src, WAVE);
-          a2[buf][u] = m2[(int64_t)j2 * F + c];
-        }
-        if (NOTHER > 3) {
-          const int32_t j3 = __shfl(i3reg, src, WAVE);
-          a3[buf][u] = m3[(int64_t)j3 * F + c];
-        }
-      }
-    };
-    auto fold = [&](int buf, int ne) {
-      #pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        if (u >= ne) break;
-        V x = vv[buf][u] * a0[buf][u] * a1[buf][u];
-        if (NOTHER > 2) x *= a2[buf][u];
-        if (NOTHER > 3) x *= a3[buf][u];
-        if (kk[buf][u] != cur) {
-          atomic_add_g(&out[(int64_t)cur * F + c], acc);
-          acc = (V)0;
-          cur = kk[buf][u];
-        }
-        acc += x;
-      }
-    };
-
-    int ne_of[NB];
-    int nbat = 0;
-    for (int ub = 0; ub < nb; ub += GB)
-      ne_of[nbat++] = nb - ub < GB ? nb - ub : GB;
-    // issue batch b+1 before folding batch b
-    issue(0, 0, ne_of[0]);
-    for (int b = 0; b < nbat; ++b) {
-      if (b + 1 < nbat) issue((b + 1) & 1, (b + 1) * GB, ne_of[b + 1]);
-      fold(b & 1, ne_of[b]);
-    }
-  }
-  atomic_add_g(&out[(int64_t)cur * F + c], acc);
-}
-
-// ----------------------------------------- vectorized-gather kernel (v4)
-// PMC evidence (profiles/): v2 runs at TA_BUSY ~87% — the per-CU vector
-// memory ADDRESS path is the bottleneck, not bandwidth or occupancy. v4
-// halves the address count: each lane gathers 16 B (VW = 16/sizeof(V)
-// columns) per factor row, so a row of F columns needs F/VW lane
-// addresses instead of F. Lane layout: L = F/VW lanes per column group,
-// R = 64/L groups; each lane folds VW columns in registers.
-template <typename V, int F, int NOTHER>
-__global__ void __launch_bounds__(256)
-mttkrp_flat4_kern(const int32_t * __restrict__ key,
-                  const int32_t * __restrict__ i0,
-                  const int32_t * __restrict__ i1,
-                  const int32_t * __restrict__ i2,
-                  const int32_t * __restrict__ i3,
-                  const V * __restrict__ m0, const V * __restrict__ m1,
-                  const V * __restrict__ m2, const V * __restrict__ m3,
-                  const V * __restrict__ vals, int64_t nnz, int64_t span,
-                  V * __restrict__ out) {
-  constexpr int VW = 16 / sizeof(V);        // columns per lane (16B loads)
-  constexpr int L = (F + VW - 1) / VW;      // lanes per column group
-  constexpr int R = WAVE / L;               // groups per wave
-  constexpr int GB = (NOTHER > 2) ? 4 : 6;  // gather batch (register budget)
-  using Vec = __attribute__((ext_vector_type(VW))) V;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wid = (int64_t)blockIdx.x * (blockDim.x / WAVE)
-                      + (threadIdx.x / WAVE);
-  const int li = lane % L;                  // lane within group
-  const int c0 = li * VW;                   // first column of this lane
-  const int g = lane / L;
-  const int gbase = g * L;
-  const int64_t w0 = wid * span;
-  if (w0 >= nnz) return;
-  const int64_t w1 = min64(nnz, w0 + span);
-  const int64_t gsz = (w1 - w0 + R - 1) / R;
-  const int64_t p0 = min64(w1, w0 + g * gsz);
-  const int64_t p1 = min64(w1, p0 + gsz);
-  if (p0 >= p1) return;
-
-  int32_t cur = key[p0];
-  V acc[VW];
-  #pragma unroll
-  for (int w = 0; w < VW; ++w) acc[w] = (V)0;
-
-  for (int64_t pb = p0; pb < p1; pb += L) {
-    const int nb = (int)min64((int64_t)L, p1 - pb);   // stream window = L
-    const int64_t ps = pb + (li < nb ? li : nb - 1);
-    const int32_t kreg = ldnt(&key[ps]);
-    const int32_t i0reg = ldnt(&i0[ps]);
-    const int32_t i1reg = ldnt(&i1[ps]);
-    const int32_t i2reg = (NOTHER > 2) ? ldnt(&i2[ps]) : 0;
-    const int32_t i3reg = (NOTHER > 3) ? ldnt(&i3[ps]) : 0;
-    const V vreg = ldnt(&vals[ps]);
-    for (int ub = 0; ub < nb; ub += GB) {
-      const int ne = nb - ub < GB ? nb - ub : GB;
-      int32_t kk[GB];
-      V vv[GB];
-      Vec a0[GB], a1[GB], a2[GB], a3[GB];
-      #pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        const int src = gbase + (u < ne ? ub + u : ub);
-        kk[u] = __shfl(kreg, src, WAVE);
-        vv[u] = __shfl(vreg, src, WAVE);
-        const int32_t j0 = __shfl(i0reg, src, WAVE);
-        const int32_t j1 = __shfl(i1reg, src, WAVE);
-        a0[u] = *reinterpret_cast<const Vec*>(&m0[(int64_t)j0 * F + c0]);
-        a1[u] = *reinterpret_cast<const Vec*>(&m1[(int64_t)j1 * F + c0]);
-        if (NOTHER > 2) {
-          const int32_t j2 = __shfl(i2reg, src, WAVE);
-          a2[u] = *reinterpret_cast<const Vec*>(&m2[(int64_t)j2 * F + c0]);
-        }
-        if (NOTHER > 3) {
-          const int32_t j3 = __shfl(i3reg, src, WAVE);
-          a3[u] = *reinterpret_cast<const Vec*>(&m3[(int64_t)j3 * F + c0]);
-        }
-      }
-      #pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        if (u >= ne) break;
-        if (kk[u] != cur) {
-          #pragma unroll
-          for (int w = 0; w < VW; ++w) {
-            atomic_add_g(&out[(int64_t)cur * F + c0 + w], acc[w]);
-            acc[w] = (V)0;
-          }
-          cur = kk[u];
-        }
-        #pragma unroll
-        for (int w = 0; w < VW; ++w) {
-          V x = vv[u] * a0[u][w] * a1[u][w];
-          if (NOTHER > 2) x *= a2[u][w];
-          if (NOTHER > 3) x *= a3[u][w];
-          acc[w] += x;
-        }
-      }
-    }
-  }
-  #pragma unroll
-  for (int w = 0; w < VW; ++w)
-    atomic_add_g(&out[(int64_t)cur * F + c0 + w], acc[w]);
 }
 
 // ------------------------------------------------------ generic-rank kernel
@@ -760,11 +447,13 @@ mttkrp_flat_generic_kern(const int32_t * __restrict__ key,
   }
 }
 
-// what v7 declines on a key stream: v2 (or the SPLATT_MTTKRP_U lever's
-// kernel) at spec ranks and <= 5 modes, the generic kernel otherwise
-template <typename V>
-void launch_flat(const int32_t * key, const int32_t * const idx[8],
-                 const V * const mats[8], const V * vals, int64_t nnz,
+// what v7 declines on a key stream: v2 at spec ranks and <= 5 modes, the
+// generic kernel otherwise. The generic kernel reads factors of the compute
+// type only: with a reduced-precision store (S != V) outside v2's shapes
+// this returns false, launching nothing.
+template <typename V, typename S>
+bool launch_flat(const int32_t * key, const int32_t * const idx[8],
+                 const S * const mats[8], const V * vals, int64_t nnz,
                  V * out, int rank, int nother, hipStream_t st) {
   const int64_t span = pick_span(nnz);
   const int64_t nwaves = (nnz + span - 1) / span;
@@ -774,79 +463,42 @@ void launch_flat(const int32_t * key, const int32_t * const idx[8],
 
 #define ARGS key, idx[0], idx[1], idx[2], idx[3], mats[0], mats[1], mats[2], \
              mats[3], vals, nnz, span, out
-#define L1(F_, N_, U_) \
-  hipLaunchKernelGGL((mttkrp_flat_kern<V, F_, N_, U_>), grid, block, 0, st, ARGS)
-#define L2K(F_, N_) \
-  hipLaunchKernelGGL((mttkrp_flat2_kern<V, F_, N_>), grid, block, 0, st, ARGS)
-#define L2K4(F_, N_) \
-  hipLaunchKernelGGL((mttkrp_flat2_kern<V, F_, N_, 4>), grid, block, 0, st, ARGS)
-#define L3K(F_, N_) \
-  hipLaunchKernelGGL((mttkrp_flat3_kern<V, F_, N_>), grid, block, 0, st, ARGS)
-#define L4K(F_, N_) \
-  hipLaunchKernelGGL((mttkrp_flat4_kern<V, F_, N_>), grid, block, 0, st, ARGS)
-#define LU(F_, N_) \
-  switch (uu) { case 4: L1(F_, N_, 4); break; case 16: L1(F_, N_, 16); break; \
-                case 8: L1(F_, N_, 8); break; case 3: L3K(F_, N_); break; \
-                case 2: L2K4(F_, N_); break; case 5: L4K(F_, N_); break; \
-                default: L2K(F_, N_); break; }
+#define L2(F_, N_) \
+  hipLaunchKernelGGL((mttkrp_flat2_kern<V, F_, N_, S>), grid, block, 0, st, ARGS)
 #define LF(N_) \
-  switch (rank) { case 4: LU(4, N_); break; case 8: LU(8, N_); break; \
-                  case 16: LU(16, N_); break; case 32: LU(32, N_); break; \
-                  default: LU(64, N_); break; }
+  switch (rank) { case 4: L2(4, N_); break; case 8: L2(8, N_); break; \
+                  case 16: L2(16, N_); break; case 32: L2(32, N_); break; \
+                  default: L2(64, N_); break; }
   if (spec_ok(rank) && nother <= 4) {
-    const int uu = pick_unroll();
     switch (nother) {
       case 2: LF(2); break;
       case 3: LF(3); break;
       default: LF(4); break;
     }
-    return;
+    return true;
   }
 #undef LF
-#undef LU
-#undef L1
+#undef L2
 #undef ARGS
-  // generic path (odd ranks or >5 modes): pointer tables travel by value
-  // in the kernel-arg block — async launch, graph-capturable, no cleanup
-  PtrTab<V> tab{};
-  for (int t = 0; t < nother; ++t) { tab.idx[t] = idx[t]; tab.mats[t] = mats[t]; }
+  if constexpr (std::is_same<S, V>::value) {
+    // generic path (odd ranks or >5 modes): pointer tables travel by value
+    // in the kernel-arg block — async launch, graph-capturable, no cleanup
+    PtrTab<V> tab{};
+    for (int t = 0; t < nother; ++t) { tab.idx[t] = idx[t]; tab.mats[t] = mats[t]; }
 #define GARGS key, tab, vals, nnz, span, rank, out
-  switch (nother) {
-    case 2:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 2>), grid, block, 0, st, GARGS); break;
-    case 3:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 3>), grid, block, 0, st, GARGS); break;
-    case 4:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 4>), grid, block, 0, st, GARGS); break;
-    case 5:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 5>), grid, block, 0, st, GARGS); break;
-    case 6:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 6>), grid, block, 0, st, GARGS); break;
-    default: hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 7>), grid, block, 0, st, GARGS); break;
-  }
+    switch (nother) {
+      case 2:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 2>), grid, block, 0, st, GARGS); break;
+      case 3:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 3>), grid, block, 0, st, GARGS); break;
+      case 4:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 4>), grid, block, 0, st, GARGS); break;
+      case 5:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 5>), grid, block, 0, st, GARGS); break;
+      case 6:  hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 6>), grid, block, 0, st, GARGS); break;
+      default: hipLaunchKernelGGL((mttkrp_flat_generic_kern<V, 7>), grid, block, 0, st, GARGS); break;
+    }
 #undef GARGS
+    return true;
+  }
+  return false;
 }
-
-#define FLAT7_SIG(V, S, VS)                                                \
-  const int32_t *, const int64_t *, int64_t, int64_t,                      \
-  const int32_t * const *, const S * const *, const VS *, int64_t, V *,    \
-  int, int
-#define FLAT_SIG(V)                                                        \
-  const int32_t *, const int32_t * const *, const V * const *, const V *,  \
-  int64_t, V *, int, int
-// Kernels land in the code object in the order they are first instantiated.
-// These keep it what it has been (the key-stream kernels of both types, then
-// the v7 instances of every type combination, then the v2 instances of the
-// reduced-precision stores), so that a change of the launcher layer leaves
-// the device code bit-identical.
-template void launch_flat<double>(FLAT_SIG(double), hipStream_t);
-template void launch_flat<float>(FLAT_SIG(float), hipStream_t);
-template bool launch_flat7<double, double, double>(
-    FLAT7_SIG(double, double, double), hipStream_t);
-template bool launch_flat7<float, float, float>(
-    FLAT7_SIG(float, float, float), hipStream_t);
-template bool launch_flat7<double, float, double>(
-    FLAT7_SIG(double, float, double), hipStream_t);
-template bool launch_flat7<double, bf16, double>(
-    FLAT7_SIG(double, bf16, double), hipStream_t);
-template bool launch_flat7<double, double, float>(
-    FLAT7_SIG(double, double, float), hipStream_t);
-#undef FLAT_SIG
 
 }  // namespace
 
@@ -866,19 +518,17 @@ int mttkrp_flat(const int32_t * key, const int64_t * rowptr, int64_t nrows,
     return launch_rc();
   // v7 declined. A key stream of V values has the older kernels behind it.
   if constexpr (std::is_same<VS, V>::value) {
-    if (rowptr) return -1;
-    if constexpr (std::is_same<S, V>::value) {
-      launch_flat<V>(key, idx, mats, vals, nnz, out, rank, nother, st);
+    if (!rowptr && launch_flat<V, S>(key, idx, mats, vals, nnz, out, rank,
+                                     nother, st))
       return launch_rc();
-    } else if (spec_ok(rank) && nother <= 4) {
-      launch_flat_store<V, S>(key, idx, mats, vals, nnz, out, rank, nother,
-                              st);
-      return launch_rc();
-    }
   }
   return -1;
 }
 
+#define FLAT7_SIG(V, S, VS)                                                \
+  const int32_t *, const int64_t *, int64_t, int64_t,                      \
+  const int32_t * const *, const S * const *, const VS *, int64_t, V *,    \
+  int, int
 // every type combination the flat family exists in
 template int mttkrp_flat<double, double, double>(
     FLAT7_SIG(double, double, double), void *);

@@ -17,7 +17,6 @@
 // depths fall back to the v2 kernel.
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include <cstdlib>
 
 #include "device_common.hpp"
 #include "launchers.hpp"
@@ -79,13 +78,8 @@ mttkrp_flat5_kern(const int32_t * __restrict__ key,
   const int c = lane % F;
   const int g = lane / F;
   const int gbase = g * F;
-  const int nsub = WPB * R;
-  const int sub = wv * R + g;
-  const int64_t total = b1 - b0;
-  const int64_t gsz = (total + nsub - 1) / nsub;
-  const int64_t p0 = min64(b1, b0 + sub * gsz);
-  const int64_t p1 = min64(b1, p0 + gsz);
-  if (p0 >= p1) return;
+  int64_t p0, p1;
+  if (!sub_range(b0, b1, wv * R + g, WPB * R, p0, p1)) return;
 
   int32_t cur = key[p0];
   V acc = (V)0;
@@ -150,9 +144,8 @@ mttkrp_flat5_kern(const int32_t * __restrict__ key,
 // S=bf16 with V=double is the documented reduced-precision factor-store
 // mode for HBM-bound shapes: gathered rows shrink 2-4x in cache lines
 // while every multiply-accumulate stays f64 (ROADMAP item 2b).
-template <typename V, int F, int NOTHER, typename S = V, int GBP = 8,
-          int WPB6K = WPB>
-__global__ void __launch_bounds__(WPB6K * WAVE)
+template <typename V, int F, int NOTHER, typename S = V>
+__global__ void __launch_bounds__(WPB * WAVE)
 mttkrp_flat6_kern(const int * __restrict__ pack_raw,
                   const S * __restrict__ m0, const S * __restrict__ m1,
                   const S * __restrict__ m2,
@@ -164,7 +157,7 @@ mttkrp_flat6_kern(const int * __restrict__ pack_raw,
                   V * __restrict__ out) {
   using Pack = __attribute__((ext_vector_type(4))) int;
   const Pack * __restrict__ pack = reinterpret_cast<const Pack *>(pack_raw);
-  constexpr int GB = (F >= GBP) ? GBP : F;
+  constexpr int GB = (F >= 8) ? 8 : F;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   S * smem = reinterpret_cast<S *>(smem_raw);
 
@@ -186,11 +179,11 @@ mttkrp_flat6_kern(const int * __restrict__ pack_raw,
       const int nvec = nel / VEC;
       const Vec * src = reinterpret_cast<const Vec *>(m0 + (int64_t)row0 * F);
       Vec * dst = reinterpret_cast<Vec *>(smem);
-      for (int ve = tid; ve < nvec; ve += WPB6K * WAVE) dst[ve] = src[ve];
-      for (int t = nvec * VEC + tid; t < nel; t += WPB6K * WAVE)
+      for (int ve = tid; ve < nvec; ve += WPB * WAVE) dst[ve] = src[ve];
+      for (int t = nvec * VEC + tid; t < nel; t += WPB * WAVE)
         smem[t] = m0[(int64_t)row0 * F + t];
     } else {
-      for (int t = tid; t < nel; t += WPB6K * WAVE)
+      for (int t = tid; t < nel; t += WPB * WAVE)
         smem[t] = m0[(int64_t)row0 * F + t];
     }
   }
@@ -202,13 +195,8 @@ mttkrp_flat6_kern(const int * __restrict__ pack_raw,
   const int c = lane % F;
   const int g = lane / F;
   const int gbase = g * F;
-  const int nsub = WPB6K * R;
-  const int sub = wv * R + g;
-  const int64_t total = b1 - b0;
-  const int64_t gsz = (total + nsub - 1) / nsub;
-  const int64_t p0 = min64(b1, b0 + sub * gsz);
-  const int64_t p1 = min64(b1, p0 + gsz);
-  if (p0 >= p1) return;
+  int64_t p0, p1;
+  if (!sub_range(b0, b1, wv * R + g, WPB * R, p0, p1)) return;
 
   int32_t cur = pack[p0].x;
   V acc = (V)0;
@@ -265,24 +253,12 @@ int mttkrp_flat6(const int32_t * pack, const S * const * mats,
                  int64_t nblocks, int32_t chunk, int32_t dim0, V * out,
                  int rank, int nother, void * stream) {
   hipStream_t st = (hipStream_t)stream;
-  const char * we = getenv("SPLATT_V6_WPB");
-  const int wpb6 = (we && atoi(we) == 8) ? 8 : WPB;
-  dim3 grid((uint32_t)nblocks), block(wpb6 * WAVE);
+  dim3 grid((uint32_t)nblocks), block(WPB * WAVE);
   const size_t lds = (size_t)chunk * rank * sizeof(S);
-  // gather-batch depth A/B lever (register pressure vs loads in flight)
-  const char * ge = getenv("SPLATT_V6_GB");
-  const int gb = ge ? atoi(ge) : 8;
 #define ARGS6 pack, mats[0], mats[1], mats[2], vals, blk_start, blk_end, \
               blk_row0, chunk, dim0, out
 #define L6(F_, N_) \
-  if (wpb6 == 8) { \
-    hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 8, 8>), grid, block, lds, st, ARGS6); \
-  } else switch (gb) { \
-    case 4:  hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 4>), grid, block, lds, st, ARGS6); break; \
-    case 6:  hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 6>), grid, block, lds, st, ARGS6); break; \
-    case 12: hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 12>), grid, block, lds, st, ARGS6); break; \
-    case 16: hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 16>), grid, block, lds, st, ARGS6); break; \
-    default: hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S, 8>), grid, block, lds, st, ARGS6); break; }
+  hipLaunchKernelGGL((mttkrp_flat6_kern<V, F_, N_, S>), grid, block, lds, st, ARGS6)
 #define L6F(N_) \
   switch (rank) { case 4: L6(4, N_); break; case 8: L6(8, N_); break; \
                   case 16: L6(16, N_); break; case 32: L6(32, N_); break; \

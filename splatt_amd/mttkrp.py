@@ -155,7 +155,7 @@ def flat_rowptr_ok(c: Csf, depth: int, rank: int) -> bool:
     """Does the unstaged flat dispatch of this mode read row pointers in
     place of the key stream? Root output of a key-sorted stream, kernel
     ranks 8/16/32/64, at most 5 modes, long runs; SPLATT_FLAT_ROWPTR=0
-    disables it. (The launcher may still decline — SPLATT_MTTKRP_U levers,
+    disables it. (The launcher may still decline — SPLATT_MTTKRP_U=1,
     streams that are not co-aligned — and the dispatch then falls back to
     the key stream.)"""
     if os.environ.get("SPLATT_FLAT_ROWPTR") == "0":

@@ -264,6 +264,24 @@ def test_levers_equivalent(monkeypatch, dims):
         assert d1 < 1e-10 and d2 < 1e-10, (m, d1, d2)
 
 
+def test_retired_lever_value_is_unset(monkeypatch):
+    """SPLATT_MTTKRP_U=8 once selected a kernel that is gone (and made the
+    row-pointer launch decline); every value but 1 now means unset."""
+    many_waves(monkeypatch)
+    dims = tuple(DIMS3)
+    cs = gpu_rand_set(dims, NNZ_BIG)
+    mats_g = [m.cuda() for m in mats_for(dims, 16)]
+    base = _all_modes(cs, mats_g, 3)
+    calls = record_rp(monkeypatch)
+    monkeypatch.setenv("SPLATT_MTTKRP_U", "8")
+    u8 = _all_modes(cs, mats_g, 3)
+    assert calls == [True] * 3
+    for m in range(3):
+        d = (base[m] - u8[m]).abs().max().item()
+        print(f"mode={m} unset-vs-U8={d:.3e}")
+        assert d < 1e-10, (m, d)
+
+
 @pytest.mark.parametrize("store", [torch.float32, torch.bfloat16])
 def test_factor_store(monkeypatch, store):
     """Same gathered values, f64 accumulation: only the staging differs."""
