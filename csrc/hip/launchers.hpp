@@ -277,5 +277,33 @@ int admm_update(const double * K, const double * Ginv, const double * rho,
                 int kind, double w, double lo, double hi, double inner_tol,
                 int max_inner, int variant, void * stream);
 
+// ------------------------------------------------------------ apr.hip
+// Poisson CPD (CP-APR) multiplicative row update of a root-sorted stream
+// (f64), rank F in 1..64, nother in 2..7, idx/mats tables of 8. B and Phi
+// are [rows, F], iters / viol0 / done have one entry per row; a slot of `ws`
+// is F doubles and slots are numbered from 0. Both return 0 or a positive
+// hipError_t (hipErrorInvalidValue for arguments out of range) and never
+// decline.
+// segments [seg0, seg0 + nseg): a single-segment row (seg_slot < 0) runs up
+// to max_inner inner iterations and stores B, Phi, iters, viol0; a segment
+// of a multi-segment row whose done flag is clear leaves the partial Phi of
+// ONE pass in slot seg_slot of `ws`.
+int apr_segments(const int32_t * const * idx, const double * const * mats,
+                 int nother, const double * vals, const int64_t * seg_start,
+                 const int32_t * seg_len, const int32_t * seg_row,
+                 const int32_t * seg_slot, int64_t seg0, int64_t nseg, int F,
+                 double eps_div, double inner_tol, int max_inner,
+                 const int32_t * done, double * ws, double * B, double * Phi,
+                 int32_t * iters, double * viol0, void * stream);
+// multi-segment rows [0, nm) that are not done: fold slots
+// mslot[m]..mslot[m+1] into Phi[mrow[m]] and finish inner iteration `round`
+// (1-based) of the row: iters = round, viol0 on round 1, then either set
+// done (violation below inner_tol > 0) or B *= Phi; done is also set on
+// round max_inner.
+int apr_fold(const double * ws, const int32_t * mrow, const int64_t * mslot,
+             int64_t nm, int F, int round, double inner_tol, int max_inner,
+             int32_t * done, double * B, double * Phi, int32_t * iters,
+             double * viol0, void * stream);
+
 }  // namespace hip
 }  // namespace splatt

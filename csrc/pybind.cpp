@@ -1017,6 +1017,63 @@ static void py_gpu_ttmc(
                             (void *)stream), "ttmc reduce");
 }
 
+// --------------------------------------- Poisson CPD / CP-APR (f64 only)
+
+// The multiplicative row update of one mode, up to max_inner inner
+// iterations, no host synchronisation. Round 1 launches every segment
+// (single-segment rows run all their iterations there) and the fold of the
+// multi-segment rows; rounds 2..max_inner relaunch the multi-segment range
+// and the fold. Segments [0, nsingle) have slot -1, the rest slots 0.. of
+// `ws` (F doubles each); `done` (one flag per row) must come in zeroed.
+static void py_hip_apr_update(
+    std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
+    Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
+    int64_t nsingle, Tensor mrow, Tensor mslot, double eps_div,
+    double inner_tol, int64_t max_inner, Tensor ws, Tensor done, Tensor B,
+    Tensor Phi, Tensor iters, Tensor viol0, int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "apr supports 3..8 modes");
+  TORCH_CHECK(max_inner >= 1 && max_inner <= 0x7FFFFFFF,
+              "max_inner must be >= 1");
+  TORCH_CHECK(eps_div > 0.0, "eps_div must be > 0");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  double * bp = dev_ptr<double>(B, "B");
+  double * pp = dev_ptr<double>(Phi, "Phi");
+  int32_t * itp = dev_ptr<int32_t>(iters, "iters");
+  double * v0p = dev_ptr<double>(viol0, "viol0");
+  int32_t * dp = dev_ptr<int32_t>(done, "done");
+  TORCH_CHECK(B.dim() == 2, "B must be [rows, rank]");
+  const int64_t rows = B.size(0);
+  const int F = (int)B.size(1);
+  TORCH_CHECK(F >= 1 && F <= 64, "apr supports rank 1..64, got ", F);
+  TORCH_CHECK(Phi.dim() == 2 && Phi.size(0) == rows && Phi.size(1) == F,
+              "Phi must have the shape of B");
+  TORCH_CHECK(iters.numel() == rows && viol0.numel() == rows
+              && done.numel() == rows,
+              "iters, viol0 and done need one entry per row of B");
+  auto ip = stream_table(idx, nother, vals.numel());
+  auto mp = factor_table<double>(mats, nother, F);
+  const int64_t nseg = seg_start.numel();
+  const int64_t nm = mrow.numel();
+  TORCH_CHECK(nsingle >= 0 && nsingle <= nseg, "nsingle out of range");
+  const SegBatch b(seg_start, seg_len, seg_row, seg_slot, 0, nseg, mrow,
+                   mslot, 0, nm, 0, nseg - nsingle, ws, F,
+                   "apr workspace too small");
+  void * st = (void *)stream;
+  for (int round = 1; round <= (int)max_inner; ++round) {
+    const int64_t seg0 = round == 1 ? 0 : nsingle;
+    check_rc(gpu::apr_segments(
+                 ip.data(), mp.data(), (int)nother, vp, b.seg_start,
+                 b.seg_len, b.seg_row, b.seg_slot, seg0, nseg - seg0, F,
+                 eps_div, inner_tol, (int)max_inner, dp, b.ws, bp, pp, itp,
+                 v0p, st), "apr segment");
+    check_rc(gpu::apr_fold(b.ws, b.mrow, b.mslot, nm, F, round, inner_tol,
+                           (int)max_inner, dp, bp, pp, itp, v0p, st),
+             "apr fold");
+    if (nm == 0) break;
+  }
+}
+
 // ------------------------------------- constrained CPD / AO-ADMM (f64 only)
 
 // The fused block-ADMM update of one factor: H and U are updated in place,
@@ -1133,6 +1190,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "row count at which the fused tail's grid reaches its cap");
   m.def("gpu_admm_update", &py_gpu_admm_update,
         "fused block-ADMM factor update (in place on H, U)");
+  m.def("hip_apr_update", &py_hip_apr_update,
+        "CP-APR multiplicative row update of a root-sorted stream (f64)");
   m.def("gpu_ttmc", &py_gpu_ttmc,
         "TTMc of a root-sorted stream: one batch of segments + row folds");
   m.def("ttmc_max_cols", &gpu::ttmc_max_cols,

@@ -22,6 +22,7 @@ from splatt_amd.admm import (AoAdmmOptions, Constraint, ConstrainedKruskal,
                              admm_solve, admm_update, box, cpd_aoadmm, l1,
                              nonneg, nonneg_l1)
 from splatt_amd.tucker import Tucker, TuckerOptions, ttmc, tucker_hooi
+from splatt_amd.apr import AprOptions, PoissonKruskal, apr_update, cpd_apr
 
 load = SpTensor.load
 
@@ -36,4 +37,5 @@ __all__ = [
     "AoAdmmOptions", "Constraint", "ConstrainedKruskal", "admm_solve",
     "admm_update", "cpd_aoadmm", "nonneg", "l1", "nonneg_l1", "box",
     "Tucker", "TuckerOptions", "ttmc", "tucker_hooi",
+    "AprOptions", "PoissonKruskal", "apr_update", "cpd_apr",
 ]

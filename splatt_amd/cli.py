@@ -123,6 +123,42 @@ def cmd_tucker(args) -> int:
     return 0
 
 
+def cmd_apr(args) -> int:
+    """`splatt apr`: Poisson CPD (CP-APR) of a count tensor. Writes
+    <stem>modeN.mat per mode and <stem>lambda.mat."""
+    import os
+    if args.dtype != "f64":
+        raise ValueError("apr supports float64 tensors only (--dtype f64)")
+    t = _load(args)
+    print(stats_tt(t, args.tensor))
+    dev = args.device
+    if dev == "auto":
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+    opts = sp.AprOptions(max_iters=args.its, max_inner=args.inner,
+                         tolerance=args.tol, seed=args.seed, verbose=True)
+    with TIMERS.time("APR"):
+        cs = sp.csf_alloc(t.to(dev), "all")
+        print(stats_csf(cs))
+        k = sp.cpd_apr(cs, args.rank, opts)
+    print(f"Final log-likelihood: {-k.loglik_trace[-1]:.8e}  KKT violation: "
+          f"{k.kkt_trace[-1]:.3e}  (iterations: {k.niters}; inner "
+          f"iterations: {sum(k.inner_trace)}; "
+          f"{'converged' if k.converged else 'not converged'})")
+    if not args.nowrite:
+        parent = os.path.dirname(args.stem)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        for m, f in enumerate(k.factors):
+            _write_matrix(f"{args.stem}mode{m + 1}.mat", f)
+        with open(f"{args.stem}lambda.mat", "w") as fh:
+            for x in k.lam.cpu().tolist():
+                fh.write(f"{x:.17g}\n")
+        print(f"wrote {len(k.factors)} factor matrices and lambda.mat with "
+              f"stem {args.stem!r}")
+    print(TIMERS.report())
+    return 0
+
+
 def parse_constraints(specs, nmodes: int):
     """`--con` specs -> per-mode list of Constraint / None.
 
@@ -470,6 +506,25 @@ def main(argv=None) -> int:
                         "PATHcore.tns (end it with / for a directory)")
     p.add_argument("--nowrite", action="store_true")
     p.set_defaults(fn=cmd_tucker)
+
+    p = sub.add_parser("apr",
+                       help="Poisson CPD of a count tensor (CP-APR)")
+    _add_common(p)
+    p.add_argument("-r", "--rank", type=int, default=10)
+    p.add_argument("-i", "--iters", "--its", dest="its", type=int,
+                   default=100)
+    p.add_argument("-t", "--tol", type=float, default=1e-4,
+                   help="KKT tolerance, outer and per row (0: run every "
+                        "iteration)")
+    p.add_argument("--inner", type=int, default=10,
+                   help="multiplicative updates per row and mode update")
+    p.add_argument("--seed", type=int, default=0x5EED5EED)
+    p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    p.add_argument("--stem", default="", metavar="PATH",
+                   help="prefix of the output files PATHmodeN.mat and "
+                        "PATHlambda.mat (end it with / for a directory)")
+    p.add_argument("--nowrite", action="store_true")
+    p.set_defaults(fn=cmd_apr)
 
     p = sub.add_parser("check", help="find/repair duplicates + empty slices")
     _add_common(p)
