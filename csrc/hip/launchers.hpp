@@ -126,9 +126,21 @@ int mttkrp_flat6(const int32_t * pack, const S * const * mats,
 // in ticks of strip_wall_khz(). Null: no waits. Two dispatches with one
 // pace buffer running at once (two streams) would share the counter: they
 // would pace wrongly, within the same bounds and with correct results; use
-// one buffer per stream. -1 = rank outside {16,32,64}, nother outside 2..3,
-// a negative budget or a stream not aligned to 128 B; -2 = the tile,
-// tile_rows * (rank + 2) * 8 bytes, exceeds the device's LDS limit.
+// one buffer per stream. Words 65 and 66 hold the sum of all workgroups'
+// waits (ticks, modulo 2^32) and the number of calls that had to poll.
+// `slots` (256 words, device, zeroed by the launcher like `pace`; or null)
+// is a ring of 8 arrival counters, word 32 x i, which replaces word 0 as the
+// thing waited on: call t of a workgroup arrives at slot t % 8 and waits for
+// all arrivals of call t - ahead, so a workgroup may run `ahead` groups
+// (0..7; 0 = the barrier) in front of the slowest; word 0 still ends at grid
+// x passes x ngroups. Needs `pace`; ahead > 0 needs `slots`. Without
+// `slots` the waits are on word 0 as before. `trace` (4 words per workgroup
+// of the grid, device, or null; needs `pace`) receives per workgroup the XCC
+// id, its wait sum, its polled calls and its longest wait.
+// -1 = rank outside {16,32,64}, nother outside 2..3, a negative budget, a
+// stream not aligned to 128 B, ahead outside 0..7 or slots / trace / ahead
+// without what they need; -2 = the tile, tile_rows * (rank + 2) * 8 bytes,
+// exceeds the device's LDS limit.
 template <typename VS>
 int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
                  const double * const * mats, const VS * vals,
@@ -136,7 +148,9 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
                  const int32_t * s_flags, const int64_t * s_bounds,
                  int ngroups, int64_t nstrips, int tile_rows, int wgs,
                  int64_t nnz, double * out, int rank, int nother,
-                 void * stream, uint32_t * pace, int pace_us);
+                 void * stream, uint32_t * pace, int pace_us,
+                 uint32_t * slots = nullptr, int ahead = 0,
+                 uint32_t * trace = nullptr);
 // Workgroups of that kernel instance resident at once on the current device
 // (occupancy x compute units): the default `wgs`. 0 when the instance does
 // not exist or the tile does not fit. Not for use during stream capture;

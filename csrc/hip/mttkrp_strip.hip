@@ -56,6 +56,27 @@
 // therefore costs one budget per workgroup, never a hang. Every workgroup
 // makes exactly passes x ngroups calls, also one with no strip in the last
 // pass. Without a pace buffer there are no waits: one unpaced launch.
+//
+// Run-ahead. A full barrier pays the slowest of the grid at every group, and
+// the pacing needs less: only that the workgroups stay within a bounded
+// stretch of the window factor. With a slots buffer (a ring of S = 8
+// counters, one 128-B line each) a workgroup's call number t (0-based,
+// continuous over groups and passes) adds 1 to slot t % S and, for t >= R,
+// waits until slot (t - R) % S has reached grid x ((t - R) / S + 1), i.e.
+// until every workgroup has arrived at ticket t - R: it may lead the slowest
+// by R groups (R + 1 while the slowest has not arrived), R = `ahead` in
+// 0..S-1, and R = 0 is the barrier again. The ring is sound because
+// S >= R + 1: a workgroup arrives at ticket t + S only after it has seen
+// ticket t + S - 1 - R >= t complete, so until every workgroup has arrived
+// at t, slot t % S counts arrivals at tickets t, t - S, t - 2S, ... only and
+// reaches the target exactly when the last one arrives. A timed-out
+// workgroup no longer waits but goes on arriving, possibly early at a later
+// ticket of a slot's class: that can only end other waits sooner, and no
+// result depends on a wait. The arrival total (word 0) is then added once
+// per workgroup at the end of the kernel, not once per call. Lane 0 also
+// sums its waits and counts the calls in which it had to poll (words 65 and
+// 66 of the pace buffer, and, with a trace buffer, four words per workgroup:
+// XCC id, wait sum, polled calls, longest wait).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -91,13 +112,24 @@ struct StripArgs {
   int64_t nnz;                 // length of the streams
   uint32_t * pace;             // PACE_* words, zeroed per launch; or null
   int64_t budget;              // longest wait, in wall_clock64() ticks
+  uint32_t * slots;            // ring of PACE_SLOTS counters, zeroed per
+                               // launch; or null: wait on PACE_ARRIVALS
+  int ahead;                   // run-ahead R, 0 .. PACE_SLOTS - 1
+  uint32_t * trace;            // [grid][4] per-workgroup words; or null
 };
 
 // words of the pace buffer, each on a 128-B line of its own
 constexpr int PACE_ARRIVALS = 0;      // pace() calls, all workgroups
 constexpr int PACE_TIMEOUTS = 32;     // workgroups that stopped waiting
 constexpr int PACE_LONGEST = 64;      // longest wait, wall_clock64() ticks
+// two more words of that line, written once per workgroup and launch
+constexpr int PACE_WAITSUM = 65;      // sum of all waits, ticks (mod 2^32)
+constexpr int PACE_POLLED = 66;       // pace() calls that had to poll
 constexpr int PACE_WORDS = 96;
+// the slot ring of the run-ahead protocol, each slot on a line of its own
+constexpr int PACE_SLOTS = 8;
+constexpr int SLOT_STRIDE = 32;
+constexpr int SLOT_WORDS = PACE_SLOTS * SLOT_STRIDE;
 
 template <int F, int NOTHER, typename VS>
 __global__ void __launch_bounds__(STRIP_THREADS)
@@ -123,21 +155,41 @@ mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
   const double * __restrict__ m2 = a.m2;
 
   // the grid barrier after a group of windows; state of the polling lane
-  uint32_t ticket = 0;
+  // ticket and waiting in registers; lane 0's statistics (longest wait, sum
+  // of waits, both in ticks and saturating, and polled calls) in LDS, since
+  // only the wait path touches them
+  uint32_t ticket = 0;           // pace() calls made so far
   bool waiting = true;
-  int64_t longest = 0;
+  __shared__ uint32_t pstat[3];
+  if (threadIdx.x == 0) pstat[0] = pstat[1] = pstat[2] = 0;
   auto pace = [&]() {
     if (!a.pace) return;
     __syncthreads();
     if (threadIdx.x == 0) {
-      uint32_t * arrivals = a.pace + PACE_ARRIVALS;
-      __hip_atomic_fetch_add(arrivals, 1u, __ATOMIC_RELAXED,
+      const uint32_t t = ticket++;
+      // the counter arrived at, and the one waited on with its target
+      uint32_t * arrive = a.pace + PACE_ARRIVALS;
+      uint32_t * watch = arrive;
+      uint32_t target = ticket * gridDim.x;
+      bool wait = waiting;
+      if (a.slots) {
+        const uint32_t R = (uint32_t)a.ahead;
+        arrive = a.slots + (t % PACE_SLOTS) * SLOT_STRIDE;
+        wait = waiting && t >= R;
+        if (wait) {
+          const uint32_t u = t - R;
+          watch = a.slots + (u % PACE_SLOTS) * SLOT_STRIDE;
+          target = (u / PACE_SLOTS + 1) * gridDim.x;
+        }
+      }
+      __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t target = ++ticket * gridDim.x;
-      if (waiting) {
+      if (wait) {
         const int64_t t0 = (int64_t)wall_clock64();
-        while (__hip_atomic_load(arrivals, __ATOMIC_RELAXED,
+        bool spun = false;
+        while (__hip_atomic_load(watch, __ATOMIC_RELAXED,
                                  __HIP_MEMORY_SCOPE_AGENT) < target) {
+          spun = true;
           if ((int64_t)wall_clock64() - t0 >= a.budget) {
             atomicAdd(a.pace + PACE_TIMEOUTS, 1u);
             waiting = false;     // sticky: no more waits in this launch
@@ -145,8 +197,14 @@ mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
           }
           __builtin_amdgcn_s_sleep(8);
         }
-        const int64_t dt = (int64_t)wall_clock64() - t0;
-        if (dt > longest) longest = dt;
+        const int64_t dt64 = (int64_t)wall_clock64() - t0;
+        const uint32_t dt =
+            (uint32_t)(dt64 < 0xFFFFFFFFll ? dt64 : 0xFFFFFFFFll);
+        if (dt > pstat[0]) pstat[0] = dt;
+        if (spun) {
+          pstat[1] = pstat[1] + dt < dt ? 0xFFFFFFFFu : pstat[1] + dt;
+          ++pstat[2];
+        }
       }
     }
     __syncthreads();
@@ -282,9 +340,25 @@ mttkrp_strip_kern(const StripArgs a, const VS * __restrict__ vals,
     // the stores of the fast workgroups overlap the walk of the slow ones
     if (a.pace) pace(); else __syncthreads();
   }
-  if (a.pace && threadIdx.x == 0 && longest > 0)
-    atomicMax(a.pace + PACE_LONGEST,
-              (uint32_t)(longest < 0xFFFFFFFFll ? longest : 0xFFFFFFFFll));
+  if (a.pace && threadIdx.x == 0) {
+    const uint32_t lw = pstat[0], ws = pstat[1], polled = pstat[2];
+    if (lw > 0) atomicMax(a.pace + PACE_LONGEST, lw);
+    if (polled > 0) {
+      atomicAdd(a.pace + PACE_WAITSUM, ws);
+      atomicAdd(a.pace + PACE_POLLED, polled);
+    }
+    // with the ring nobody waits on the total: one add per workgroup
+    if (a.slots) atomicAdd(a.pace + PACE_ARRIVALS, ticket);
+    if (a.trace) {
+      // HW_REG_XCC_ID, bits 3:0: the XCD this workgroup ran on
+      const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));
+      uint32_t * tr = a.trace + (size_t)blockIdx.x * 4;
+      tr[0] = xcc;
+      tr[1] = ws;
+      tr[2] = polled;
+      tr[3] = lw;
+    }
+  }
 }
 
 // largest dynamic LDS request a block may make on the current device
@@ -366,6 +440,11 @@ int strip_inst(const StripLaunch * L, int lds, int * wgs) {
         L->a.pace, 0, PACE_WORDS * sizeof(uint32_t), L->st);
     if (e != hipSuccess) return (int)e;
   }
+  if (L->a.slots) {
+    const hipError_t e = hipMemsetAsync(
+        L->a.slots, 0, SLOT_WORDS * sizeof(uint32_t), L->st);
+    if (e != hipSuccess) return (int)e;
+  }
   const int64_t n = L->nstrips < L->wgs ? L->nstrips : L->wgs;
   hipLaunchKernelGGL(kern, dim3((uint32_t)n), dim3(STRIP_THREADS),
                      (size_t)lds, L->st, L->a,
@@ -412,9 +491,13 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
                  const int32_t * s_flags, const int64_t * s_bounds,
                  int ngroups, int64_t nstrips, int tile_rows, int wgs,
                  int64_t nnz, double * out, int rank, int nother,
-                 void * stream, uint32_t * pace, int pace_us) {
+                 void * stream, uint32_t * pace, int pace_us,
+                 uint32_t * slots, int ahead, uint32_t * trace) {
   if (nstrips <= 0) return 0;
   if (wgs < 1 || ngroups < 1 || nother < 2 || nother > 3 || pace_us < 0)
+    return -1;
+  if (ahead < 0 || ahead >= PACE_SLOTS || (ahead > 0 && !slots)
+      || ((slots || trace) && !pace))
     return -1;
   // windows are the streams' 128-B lines
   uintptr_t bits = (uintptr_t)key | (uintptr_t)vals;
@@ -423,7 +506,7 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
   StripLaunch L{{key, idx[0], idx[1], nother > 2 ? idx[2] : nullptr, mats[0],
                  mats[1], nother > 2 ? mats[2] : nullptr, s_row0, s_nrows,
                  s_flags, s_bounds, ngroups, nnz, pace,
-                 (int64_t)pace_us * wall_khz() / 1000},
+                 (int64_t)pace_us * wall_khz() / 1000, slots, ahead, trace},
                 vals, nstrips, wgs, tile_rows, out, (hipStream_t)stream};
   return strip_dispatch<VS>(&L, tile_rows, rank, nother, nullptr);
 }
@@ -432,7 +515,7 @@ int mttkrp_strip(const int32_t * key, const int32_t * const * idx,
   const int32_t *, const int32_t * const *, const double * const *,        \
   const VS *, const int32_t *, const int32_t *, const int32_t *,           \
   const int64_t *, int, int64_t, int, int, int64_t, double *, int, int,    \
-  void *, uint32_t *, int
+  void *, uint32_t *, int, uint32_t *, int, uint32_t *
 template int mttkrp_strip<double>(STRIP_SIG(double));
 template int mttkrp_strip<float>(STRIP_SIG(float));
 #undef STRIP_SIG

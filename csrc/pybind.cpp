@@ -581,13 +581,17 @@ static bool py_gpu_mttkrp_flat_v32(c10::optional<Tensor> rowptr, int64_t p0,
 // f64 factors and output. Returns false when the launcher declines
 // (misaligned streams, tile above the LDS limit) — the caller then takes the
 // key-stream kernel. `pace` (96 words of uint32 or int32, or None: no
-// waits) and `pace_us` are the pace buffer and wait budget of launchers.hpp.
+// waits) and `pace_us` are the pace buffer and wait budget of launchers.hpp;
+// `slots` (256 words, or None), `ahead` and `trace` (4 words per workgroup,
+// or None) its slot ring, run-ahead and per-workgroup trace.
 static bool py_mttkrp_strip_gpu(Tensor key, std::vector<Tensor> idx,
                                 std::vector<Tensor> mats, Tensor vals,
                                 Tensor s_row0, Tensor s_nrows, Tensor s_flags,
                                 Tensor s_bounds, int64_t tile_rows,
                                 int64_t wgs, Tensor out, int64_t stream,
-                                c10::optional<Tensor> pace, int64_t pace_us) {
+                                c10::optional<Tensor> pace, int64_t pace_us,
+                                c10::optional<Tensor> slots, int64_t ahead,
+                                c10::optional<Tensor> trace) {
   const size_t nother = idx.size();
   TORCH_CHECK(nother >= 2 && nother <= 3, "strip kernel supports 3..4 modes");
   TORCH_CHECK(tile_rows >= 1 && tile_rows <= (1 << 20) && wgs >= 1
@@ -622,17 +626,40 @@ static bool py_mttkrp_strip_gpu(Tensor key, std::vector<Tensor> idx,
   }
   TORCH_CHECK(pace_us >= 0 && pace_us <= 60 * 1000 * 1000,
               "pace_us out of range");
+  // words of a pace-side buffer: device, 32-bit integers, contiguous
+  auto words = [](const Tensor & p, const char * what, int64_t need) {
+    TORCH_CHECK(p.is_cuda(), what, " must be a device tensor");
+    TORCH_CHECK(p.scalar_type() == torch::kInt32
+                || p.scalar_type() == at::ScalarType::UInt32,
+                what, " has dtype ", p.scalar_type(),
+                ", expected Int or UInt32");
+    TORCH_CHECK(p.is_contiguous() && p.numel() >= need, what,
+                " must be contiguous and hold at least ", need, " words");
+    return static_cast<uint32_t *>(p.data_ptr());
+  };
+  TORCH_CHECK(ahead >= 0 && ahead <= 7, "ahead out of range 0..7");
+  uint32_t * sp_ = nullptr, * tp = nullptr;
+  if (slots.has_value()) {
+    TORCH_CHECK(pp != nullptr, "slots need a pace tensor");
+    sp_ = words(*slots, "slots", 256);
+  }
+  TORCH_CHECK(ahead == 0 || sp_ != nullptr,
+              "ahead > 0 needs pace and slots tensors");
+  if (trace.has_value()) {
+    TORCH_CHECK(pp != nullptr, "trace needs a pace tensor");
+    tp = words(*trace, "trace", 4 * std::min<int64_t>(wgs, ns));
+  }
   const int rc = vals.scalar_type() == torch::kFloat32
       ? gpu::mttkrp_strip<float>(kp, ip.data(), mp.data(),
                                  dev_ptr<float>(vals, "vals"), r0, nr, fl, bp,
                                  ng, ns, (int)tile_rows, (int)wgs, nnz, op,
                                  rank, (int)nother, (void *)stream, pp,
-                                 (int)pace_us)
+                                 (int)pace_us, sp_, (int)ahead, tp)
       : gpu::mttkrp_strip<double>(kp, ip.data(), mp.data(),
                                   dev_ptr<double>(vals, "vals"), r0, nr, fl,
                                   bp, ng, ns, (int)tile_rows, (int)wgs, nnz,
                                   op, rank, (int)nother, (void *)stream, pp,
-                                  (int)pace_us);
+                                  (int)pace_us, sp_, (int)ahead, tp);
   if (rc > 0) check_rc(rc, "strip MTTKRP");
   return rc == 0;
 }
@@ -1228,7 +1255,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("s_row0"), py::arg("s_nrows"), py::arg("s_flags"),
         py::arg("s_bounds"), py::arg("tile_rows"), py::arg("wgs"),
         py::arg("out"), py::arg("stream"), py::arg("pace") = py::none(),
-        py::arg("pace_us") = 3600);
+        py::arg("pace_us") = 2200, py::arg("slots") = py::none(),
+        py::arg("ahead") = 0, py::arg("trace") = py::none());
   m.def("strip_wall_khz", &gpu::strip_wall_khz,
         "rate of the wall clock of the strip kernel's pace words, kHz");
   m.def("strip_wgs", &gpu::strip_wgs,

@@ -12,7 +12,8 @@ VERSION = (0, 1, 0)
 
 from splatt_amd.sptensor import SpTensor
 from splatt_amd.csf import Csf, CsfSet, CsfAllocPolicy, build_csf, csf_alloc, order_modes
-from splatt_amd.mttkrp import mttkrp, mttkrp_stream, strip_pace_stats
+from splatt_amd.mttkrp import (mttkrp, mttkrp_stream, strip_pace_stats,
+                               strip_pace_waits)
 from splatt_amd.cpd import CpdOptions, Kruskal, cpd_als, cpd_als_cpu_native, seeded_init
 from splatt_amd.kruskal import (kruskal_fit, kruskal_innerprod, kruskal_norm,
                                 kruskal_to_dense)
@@ -29,6 +30,7 @@ load = SpTensor.load
 __all__ = [
     "SpTensor", "Csf", "CsfSet", "CsfAllocPolicy", "build_csf", "csf_alloc",
     "order_modes", "mttkrp", "mttkrp_stream", "strip_pace_stats",
+    "strip_pace_waits",
     "CpdOptions", "Kruskal",
     "cpd_als", "cpd_als_cpu_native", "seeded_init", "load",
     "kruskal_fit", "kruskal_innerprod", "kruskal_norm", "kruskal_to_dense",

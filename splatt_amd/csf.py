@@ -340,9 +340,10 @@ def _strip_wgs(rank: int, nother: int, tile_rows: int) -> int:
 
 
 # factor bytes of the window level per pace group: the workgroups of the
-# launch stay within this much of the factor (measured default,
-# profiles/amazon_strip_paced.md); SPLATT_STRIP_GROUP_KB overrides
-STRIP_GROUP_KB = 16384
+# launch stay within this much of the factor, times 1 + the run-ahead of
+# mttkrp.py STRIP_AHEAD (measured default of the pair,
+# profiles/amazon_strip_ahead.md); SPLATT_STRIP_GROUP_KB overrides
+STRIP_GROUP_KB = 8192
 
 
 def _strip_groups(factor_bytes: int) -> int:
@@ -511,6 +512,9 @@ def _build_csf_device(t: SpTensor, perm: List[int],
         # the kernel's pace words (arrivals, time-outs, longest wait; 96
         # words, csrc/hip/launchers.hpp), cleared by every dispatch
         strip_meta["pace"] = torch.zeros(96, dtype=torch.int32, device=dev)
+        # and the ring of 8 arrival counters of its run-ahead pacing, one
+        # 128-B line each
+        strip_meta["slots"] = torch.zeros(256, dtype=torch.int32, device=dev)
     sinds = [t.inds[perm[l]].index_select(0, order) for l in range(nm)]
     svals = t.vals.index_select(0, order)
 

@@ -372,14 +372,19 @@ def _gpu_mttkrp_flat(c: Csf, depth: int, mats: List[torch.Tensor],
             ms = [mats[c.dim_perm[l]].contiguous() for l in lv]
             v32 = _vals32(c, rank, mats)
             # one launch, its workgroups paced group by group through the
-            # CSF's pace words (SPLATT_STRIP_PACE=0: no waits)
+            # CSF's pace words and slot ring, each allowed to lead the
+            # slowest by SPLATT_STRIP_AHEAD groups (SPLATT_STRIP_PACE=0: no
+            # waits)
             paced = os.environ.get("SPLATT_STRIP_PACE") != "0"
             if native().mttkrp_strip_gpu(
                     key.contiguous(), idx, ms, c.vals if v32 is None else v32,
                     strip["row0"], strip["nrows"], strip["flags"],
                     strip["bounds"], strip["tile_rows"],
                     strip["wgs"], out, stream,
-                    strip["pace"] if paced else None, _strip_pace_us()):
+                    strip["pace"] if paced else None, _strip_pace_us(),
+                    strip["slots"] if paced else None,
+                    _strip_ahead() if paced else 0,
+                    _strip_trace(strip) if paced else None):
                 return
     p0, p1 = 0, c.nnz
     if rows is not None:
@@ -423,14 +428,56 @@ def factor_store_dtype():
 
 # longest wait of a workgroup at one pace point of the strip kernel, in
 # microseconds: 4x the longest wait of a bench.py run on the Amazon shape
-# (880 us, profiles/amazon_strip_paced.md), since waits grow with the group
-# size and the imbalance of a pass; SPLATT_STRIP_PACE_US overrides
-STRIP_PACE_US = 3600
+# (547 us at 8 MiB groups, profiles/amazon_strip_ahead.md), rounded up, since
+# waits grow with the group size and the imbalance of a pass;
+# SPLATT_STRIP_PACE_US overrides
+STRIP_PACE_US = 2200
 
 
 def _strip_pace_us() -> int:
     return max(0, int(os.environ.get("SPLATT_STRIP_PACE_US",
                                      str(STRIP_PACE_US))))
+
+
+# groups a workgroup of the strip kernel may lead the slowest one by (0..7;
+# 0 = a full barrier after every group); measured default together with
+# csf.py STRIP_GROUP_KB (profiles/amazon_strip_ahead.md: more run-ahead
+# waits less but spreads the workgroups over more of the window factor);
+# SPLATT_STRIP_AHEAD overrides
+STRIP_AHEAD = 1
+
+
+def _strip_ahead() -> int:
+    r = int(os.environ.get("SPLATT_STRIP_AHEAD", str(STRIP_AHEAD)))
+    if not 0 <= r <= 7:
+        raise ValueError(f"SPLATT_STRIP_AHEAD must be in 0..7, got {r}")
+    return r
+
+
+def _strip_trace(strip: dict):
+    """Per-workgroup trace words of the strip kernel ([grid, 4]: XCC id, wait
+    sum in ticks, polled waits, longest wait in ticks), only with
+    SPLATT_STRIP_TRACE=1; allocated on the first such dispatch outside
+    stream capture and kept in the CSF's strip dictionary."""
+    if os.environ.get("SPLATT_STRIP_TRACE") != "1":
+        return None
+    tr = strip.get("trace")
+    if tr is None and not torch.cuda.is_current_stream_capturing():
+        grid = min(int(strip["wgs"]), int(strip["row0"].numel()))
+        tr = torch.zeros(grid, 4, dtype=torch.int32,
+                         device=strip["pace"].device)
+        strip["trace"] = tr
+    return tr
+
+
+def strip_pace_waits(c: Csf) -> tuple:
+    """(sum over all workgroups of the time spent waiting at pace points, in
+    microseconds; number of pace calls that had to poll) of the last strip
+    dispatch of a strip-layout CSF. Synchronises the device."""
+    words = c._strip["pace"].cpu().tolist()   # type: ignore[attr-defined]
+    khz = native().strip_wall_khz()
+    return ((words[65] & 0xFFFFFFFF) * 1000.0 / khz if khz > 0 else 0.0,
+            words[66] & 0xFFFFFFFF)
 
 
 def strip_pace_stats(c: Csf) -> tuple:
