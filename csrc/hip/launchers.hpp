@@ -319,5 +319,30 @@ int apr_fold(const double * ws, const int32_t * mrow, const int64_t * mslot,
              int32_t * done, double * B, double * Phi, int32_t * iters,
              double * viol0, void * stream);
 
+// ------------------------------------------------------------ gcp.hip
+// Generalized CPD loss-gradient pass of a root-sorted stream (f64), rank F
+// in 1..64, nother in 2..7, idx/mats tables of 8. A (the output mode's
+// factor) and G are [rows, F]. loss: 0 gaussian, 1 huber, 2 poisson,
+// 3 poisson-log, 4 bernoulli-odds, 5 bernoulli-logit, 6 gamma, 7 rayleigh;
+// `param` is huber's delta and unused otherwise. frow (one entry per row)
+// may be null: the loss value is then not computed, and a slot of `ws` is F
+// doubles; with frow it is F + 1. Slots are numbered from 0. Both return 0
+// or a positive hipError_t (hipErrorInvalidValue for arguments out of range)
+// and never decline. Rows without entries are not written: G and frow come
+// in zeroed.
+// segments [0, nseg): a single-segment row (seg_slot < 0) stores
+// G[row] = sum dl/dm(val, mdl) pi and frow[row] = sum l(val, mdl); a segment
+// of a multi-segment row leaves its partial sums in slot seg_slot of `ws`.
+int gcp_segments(const int32_t * const * idx, const double * const * mats,
+                 int nother, const double * vals, const int64_t * seg_start,
+                 const int32_t * seg_len, const int32_t * seg_row,
+                 const int32_t * seg_slot, int64_t nseg, int F, int loss,
+                 double param, const double * A, double * ws, double * G,
+                 double * frow, void * stream);
+// multi-segment rows [0, nm): fold slots mslot[m]..mslot[m+1] in order into
+// G[mrow[m]] (and frow[mrow[m]]); frow null or not as in gcp_segments.
+int gcp_fold(const double * ws, const int32_t * mrow, const int64_t * mslot,
+             int64_t nm, int F, double * G, double * frow, void * stream);
+
 }  // namespace hip
 }  // namespace splatt

@@ -1101,6 +1101,57 @@ static void py_hip_apr_update(
   }
 }
 
+// ------------------------------------- generalized CPD / GCP (f64 only)
+
+// The loss-gradient pass of one mode: G[i] = sum dl/dm(val, mdl) pi over the
+// stored entries of row i, and frow[i] = sum l(val, mdl) when frow is given.
+// One launch of every segment and, if the plan has multi-segment rows, one
+// fold; no host synchronisation. Segments [0, nsingle) have slot -1, the
+// rest slots 0.. of `ws` (F doubles each, F + 1 with frow). G and frow must
+// come in zeroed: rows without entries are not written.
+static void py_hip_gcp_grad(
+    std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
+    Tensor seg_start, Tensor seg_len, Tensor seg_row, Tensor seg_slot,
+    int64_t nsingle, Tensor mrow, Tensor mslot, int64_t loss, double param,
+    Tensor A, Tensor ws, Tensor G, py::object frow, int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "gcp supports 3..8 modes");
+  TORCH_CHECK(loss >= 0 && loss <= 7, "gcp loss id must be 0..7, got ", loss);
+  TORCH_CHECK(loss != 1 || param > 0.0, "huber needs param > 0");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  const double * ap = dev_ptr<double>(A, "A");
+  double * gp = dev_ptr<double>(G, "G");
+  TORCH_CHECK(A.dim() == 2, "A must be [rows, rank]");
+  const int64_t rows = A.size(0);
+  const int F = (int)A.size(1);
+  TORCH_CHECK(F >= 1 && F <= 64, "gcp supports rank 1..64, got ", F);
+  TORCH_CHECK(G.dim() == 2 && G.size(0) == rows && G.size(1) == F,
+              "G must have the shape of A");
+  double * fp = nullptr;
+  Tensor ft;
+  if (!frow.is_none()) {
+    ft = frow.cast<Tensor>();
+    fp = dev_ptr<double>(ft, "frow");
+    TORCH_CHECK(ft.numel() == rows, "frow needs one entry per row of A");
+  }
+  auto ip = stream_table(idx, nother, vals.numel());
+  auto mp = factor_table<double>(mats, nother, F);
+  const int64_t nseg = seg_start.numel();
+  const int64_t nm = mrow.numel();
+  TORCH_CHECK(nsingle >= 0 && nsingle <= nseg, "nsingle out of range");
+  const SegBatch b(seg_start, seg_len, seg_row, seg_slot, 0, nseg, mrow,
+                   mslot, 0, nm, 0, nseg - nsingle, ws, F + (fp ? 1 : 0),
+                   "gcp workspace too small");
+  void * st = (void *)stream;
+  check_rc(gpu::gcp_segments(
+               ip.data(), mp.data(), (int)nother, vp, b.seg_start, b.seg_len,
+               b.seg_row, b.seg_slot, nseg, F, (int)loss, param, ap, b.ws, gp,
+               fp, st), "gcp segment");
+  if (nm > 0)
+    check_rc(gpu::gcp_fold(b.ws, b.mrow, b.mslot, nm, F, gp, fp, st),
+             "gcp fold");
+}
+
 // ------------------------------------- constrained CPD / AO-ADMM (f64 only)
 
 // The fused block-ADMM update of one factor: H and U are updated in place,
@@ -1219,6 +1270,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused block-ADMM factor update (in place on H, U)");
   m.def("hip_apr_update", &py_hip_apr_update,
         "CP-APR multiplicative row update of a root-sorted stream (f64)");
+  m.def("hip_gcp_grad", &py_hip_gcp_grad,
+        "GCP loss-gradient pass of a root-sorted stream (f64)");
   m.def("gpu_ttmc", &py_gpu_ttmc,
         "TTMc of a root-sorted stream: one batch of segments + row folds");
   m.def("ttmc_max_cols", &gpu::ttmc_max_cols,

@@ -24,6 +24,8 @@ from splatt_amd.admm import (AoAdmmOptions, Constraint, ConstrainedKruskal,
                              nonneg, nonneg_l1)
 from splatt_amd.tucker import Tucker, TuckerOptions, ttmc, tucker_hooi
 from splatt_amd.apr import AprOptions, PoissonKruskal, apr_update, cpd_apr
+from splatt_amd.gcp import (GcpKruskal, GcpOptions, cpd_gcp, gcp_fg, gcp_grad,
+                            sample_zeros)
 
 load = SpTensor.load
 
@@ -40,4 +42,6 @@ __all__ = [
     "admm_update", "cpd_aoadmm", "nonneg", "l1", "nonneg_l1", "box",
     "Tucker", "TuckerOptions", "ttmc", "tucker_hooi",
     "AprOptions", "PoissonKruskal", "apr_update", "cpd_apr",
+    "GcpOptions", "GcpKruskal", "gcp_grad", "gcp_fg", "cpd_gcp",
+    "sample_zeros",
 ]

@@ -159,6 +159,47 @@ def cmd_apr(args) -> int:
     return 0
 
 
+def cmd_gcp(args) -> int:
+    """`splatt gcp`: generalized CPD of the stored entries under an
+    elementwise loss. Writes <stem>modeN.mat per mode and <stem>lambda.mat."""
+    import os
+    if args.dtype != "f64":
+        raise ValueError("gcp supports float64 tensors only (--dtype f64)")
+    t = _load(args)
+    print(stats_tt(t, args.tensor))
+    dev = args.device
+    if dev == "auto":
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+    opts = sp.GcpOptions(max_iters=args.its, tolerance=args.tol,
+                         seed=args.seed, param=args.param, verbose=True)
+    with TIMERS.time("GCP"):
+        t = t.to(dev)
+        if args.zeros:
+            t = sp.sample_zeros(t, args.zeros, args.seed)
+            print(f"stored {args.zeros} sampled zeros: {t.nnz} observed "
+                  "entries")
+        cs = sp.csf_alloc(t, "all")
+        print(stats_csf(cs))
+        k = sp.cpd_gcp(cs, args.rank, args.loss, opts)
+    final = k.loss_trace[-1] if k.loss_trace else float("nan")
+    print(f"Final loss: {final:.8e}  ({args.loss}; iterations: {k.niters}; "
+          f"evaluations: {k.nfev}; "
+          f"{'converged' if k.converged else 'not converged'})")
+    if not args.nowrite:
+        parent = os.path.dirname(args.stem)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        for m, f in enumerate(k.factors):
+            _write_matrix(f"{args.stem}mode{m + 1}.mat", f)
+        with open(f"{args.stem}lambda.mat", "w") as fh:
+            for x in k.lam.cpu().tolist():
+                fh.write(f"{x:.17g}\n")
+        print(f"wrote {len(k.factors)} factor matrices and lambda.mat with "
+              f"stem {args.stem!r}")
+    print(TIMERS.report())
+    return 0
+
+
 def parse_constraints(specs, nmodes: int):
     """`--con` specs -> per-mode list of Constraint / None.
 
@@ -525,6 +566,31 @@ def main(argv=None) -> int:
                         "PATHlambda.mat (end it with / for a directory)")
     p.add_argument("--nowrite", action="store_true")
     p.set_defaults(fn=cmd_apr)
+
+    from splatt_amd.gcp import LOSSES as _gcp_losses
+    p = sub.add_parser("gcp",
+                       help="generalized CPD of the stored entries under an "
+                            "elementwise loss (GCP)")
+    _add_common(p)
+    p.add_argument("-r", "--rank", type=int, default=10)
+    p.add_argument("--loss", default="gaussian", choices=list(_gcp_losses))
+    p.add_argument("--param", type=float, default=None,
+                   help="loss parameter (huber: delta)")
+    p.add_argument("-i", "--iters", "--its", dest="its", type=int,
+                   default=200)
+    p.add_argument("-t", "--tol", type=float, default=1e-6,
+                   help="stop when the loss decreases by less than this, "
+                        "relatively (0: run every iteration)")
+    p.add_argument("--zeros", type=int, default=0, metavar="N",
+                   help="store N zeros sampled from the empty cells first "
+                        "(binary data: positives plus sampled negatives)")
+    p.add_argument("--seed", type=int, default=0x5EED5EED)
+    p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    p.add_argument("--stem", default="", metavar="PATH",
+                   help="prefix of the output files PATHmodeN.mat and "
+                        "PATHlambda.mat (end it with / for a directory)")
+    p.add_argument("--nowrite", action="store_true")
+    p.set_defaults(fn=cmd_gcp)
 
     p = sub.add_parser("check", help="find/repair duplicates + empty slices")
     _add_common(p)
