@@ -344,5 +344,32 @@ int gcp_segments(const int32_t * const * idx, const double * const * mats,
 int gcp_fold(const double * ws, const int32_t * mrow, const int64_t * mslot,
              int64_t nm, int F, double * G, double * frow, void * stream);
 
+// ------------------------------------------------------------ sgcp.hip
+// Stochastic GCP (f64). A sample is n = p + q coordinates, stored draws
+// first: inds is [nmodes, n] int32 row-major, vals [n] (0 for the cell
+// draws). mats/grads are host tables of nmodes device pointers, [dims[t], F]
+// each, nmodes in 3..8, F in 1..64, loss and param as for gcp.hip. Adds the
+// semi-stratified gradient estimate (weights wnz for stored draws, wz for
+// cell draws) into grads with f64 atomics: grads come in zeroed, and the
+// result is not bitwise reproducible. Every index must lie inside its
+// factor: nothing is checked on the device. partials may be null; otherwise
+// it has at least sgcp_nparts(n, nmodes, F) entries, every one of which is
+// written, and their sum is the loss estimate. Returns 0 or a positive
+// hipError_t (hipErrorInvalidValue for arguments out of range).
+int64_t sgcp_nparts(int64_t n, int nmodes, int F);
+int sgcp_grad(const int32_t * inds, const double * vals, int64_t n, int64_t p,
+              const double * const * mats, double * const * grads, int nmodes,
+              int F, int loss, double param, double wnz, double wz,
+              double * partials, void * stream);
+// One Adam step on flat buffers of n doubles, in place:
+//   m = beta1 m + (1 - beta1) g;  v = beta2 v + ((1 - beta2) g) g
+//   x = x - (lr (m c1)) / (sqrt(v c2) + eps);  x = max(x, lower) if bounded
+//   g = 0
+// c1, c2 are the bias corrections 1 / (1 - beta^step), computed by the
+// caller. No contraction: every operation rounds once.
+int adam_step(double * x, double * g, double * m, double * v, int64_t n,
+              double lr, double beta1, double beta2, double eps, double c1,
+              double c2, bool bounded, double lower, void * stream);
+
 }  // namespace hip
 }  // namespace splatt

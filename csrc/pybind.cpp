@@ -1152,6 +1152,77 @@ static void py_hip_gcp_grad(
              "gcp fold");
 }
 
+// ------------------------------------------- stochastic GCP (f64 only)
+
+// The sampled-gradient pass: adds the semi-stratified estimate of every
+// mode's gradient into grads (which come in zeroed) from the sample
+// inds [nmodes, n] / vals [n], whose first p entries are stored draws.
+// Returns the number of entries of `partials` that were written (their sum
+// is the loss estimate), 0 without partials. Index VALUES are not checked:
+// the caller guarantees inds[t] < mats[t].size(0).
+static int64_t py_hip_sgcp_grad(Tensor inds, Tensor vals, int64_t p,
+                                std::vector<Tensor> mats,
+                                std::vector<Tensor> grads, int64_t loss,
+                                double param, double wnz, double wz,
+                                py::object partials, int64_t stream) {
+  const int32_t * ip = dev_ptr<int32_t>(inds, "inds");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  const size_t nm = mats.size();
+  TORCH_CHECK(nm >= 3 && nm <= 8, "sgcp supports 3..8 modes");
+  TORCH_CHECK(loss >= 0 && loss <= 7, "gcp loss id must be 0..7, got ", loss);
+  TORCH_CHECK(loss != 1 || param > 0.0, "huber needs param > 0");
+  const int64_t n = vals.numel();
+  TORCH_CHECK(inds.dim() == 2 && inds.size(0) == (int64_t)nm
+              && inds.size(1) == n, "inds must be [nmodes, p + q]");
+  TORCH_CHECK(n >= 1 && p >= 0 && p <= n, "p out of range");
+  const int F = rank_of(mats);
+  TORCH_CHECK(F >= 1 && F <= 64, "sgcp supports rank 1..64, got ", F);
+  auto mp = factor_table<double>(mats, nm, F);
+  TORCH_CHECK(grads.size() == nm, "expected ", nm, " grads, got ",
+              grads.size());
+  std::array<double *, 8> gp{};
+  for (size_t t = 0; t < nm; ++t) {
+    gp[t] = dev_ptr<double>(grads[t], "grad");
+    TORCH_CHECK(grads[t].sizes() == mats[t].sizes(),
+                "grad ", t, " must have the shape of factor ", t);
+    TORCH_CHECK(mats[t].size(0) <= 0x7FFFFFFF, "factor rows must fit int32");
+  }
+  double * pp = nullptr;
+  int64_t nparts = 0;
+  Tensor pt;
+  if (!partials.is_none()) {
+    pt = partials.cast<Tensor>();
+    pp = dev_ptr<double>(pt, "partials");
+    nparts = gpu::sgcp_nparts(n, (int)nm, F);
+    TORCH_CHECK(pt.numel() >= nparts, "partials needs ", nparts,
+                " entries, got ", pt.numel());
+  }
+  check_rc(gpu::sgcp_grad(ip, vp, n, p, mp.data(), gp.data(), (int)nm, F,
+                          (int)loss, param, wnz, wz, pp, (void *)stream),
+           "sgcp grad");
+  return nparts;
+}
+
+// One fused Adam step on flat f64 buffers (launchers.hpp: adam_step).
+static void py_hip_adam_step(Tensor x, Tensor g, Tensor m, Tensor v, double lr,
+                             double beta1, double beta2, double eps, double c1,
+                             double c2, c10::optional<double> lower,
+                             int64_t stream) {
+  double * xp = dev_ptr<double>(x, "x");
+  double * gp = dev_ptr<double>(g, "g");
+  double * mp = dev_ptr<double>(m, "m");
+  double * vp = dev_ptr<double>(v, "v");
+  const int64_t n = x.numel();
+  TORCH_CHECK(x.dim() == 1 && g.dim() == 1 && m.dim() == 1 && v.dim() == 1
+              && g.numel() == n && m.numel() == n && v.numel() == n,
+              "x, g, m and v must be flat buffers of one length");
+  TORCH_CHECK(xp != gp && xp != mp && xp != vp && gp != mp && gp != vp
+              && mp != vp, "x, g, m and v must not alias");
+  check_rc(gpu::adam_step(xp, gp, mp, vp, n, lr, beta1, beta2, eps, c1, c2,
+                          lower.has_value(), lower.value_or(0.0),
+                          (void *)stream), "adam step");
+}
+
 // ------------------------------------- constrained CPD / AO-ADMM (f64 only)
 
 // The fused block-ADMM update of one factor: H and U are updated in place,
@@ -1272,6 +1343,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "CP-APR multiplicative row update of a root-sorted stream (f64)");
   m.def("hip_gcp_grad", &py_hip_gcp_grad,
         "GCP loss-gradient pass of a root-sorted stream (f64)");
+  m.def("hip_sgcp_grad", &py_hip_sgcp_grad,
+        "stochastic GCP: sampled gradient of every mode, atomics (f64)");
+  m.def("hip_adam_step", &py_hip_adam_step,
+        "fused Adam step on flat f64 buffers, g left zeroed");
   m.def("gpu_ttmc", &py_gpu_ttmc,
         "TTMc of a root-sorted stream: one batch of segments + row folds");
   m.def("ttmc_max_cols", &gpu::ttmc_max_cols,

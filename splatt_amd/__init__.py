@@ -26,6 +26,8 @@ from splatt_amd.tucker import Tucker, TuckerOptions, ttmc, tucker_hooi
 from splatt_amd.apr import AprOptions, PoissonKruskal, apr_update, cpd_apr
 from splatt_amd.gcp import (GcpKruskal, GcpOptions, cpd_gcp, gcp_fg, gcp_grad,
                             sample_zeros)
+from splatt_amd.sgcp import (GcpSample, SgcpKruskal, SgcpOptions, adam_step,
+                             cpd_sgcp, gcp_sample, gcp_sgrad)
 
 load = SpTensor.load
 
@@ -44,4 +46,6 @@ __all__ = [
     "AprOptions", "PoissonKruskal", "apr_update", "cpd_apr",
     "GcpOptions", "GcpKruskal", "gcp_grad", "gcp_fg", "cpd_gcp",
     "sample_zeros",
+    "GcpSample", "SgcpOptions", "SgcpKruskal", "gcp_sample", "gcp_sgrad",
+    "adam_step", "cpd_sgcp",
 ]

@@ -200,6 +200,43 @@ def cmd_gcp(args) -> int:
     return 0
 
 
+def cmd_sgcp(args) -> int:
+    """`splatt sgcp`: stochastic generalized CPD over ALL cells (unstored
+    cells are zeros) by Adam on sampled gradients. Writes <stem>modeN.mat
+    per mode and <stem>lambda.mat."""
+    import os
+    if args.dtype != "f64":
+        raise ValueError("sgcp supports float64 tensors only (--dtype f64)")
+    t = _load(args)
+    print(stats_tt(t, args.tensor))
+    dev = args.device
+    if dev == "auto":
+        dev = "cuda" if torch.cuda.is_available() else "cpu"
+    opts = sp.SgcpOptions(p=args.p, q=args.q, lr=args.lr, decay=args.decay,
+                          max_fails=args.fails,
+                          iters_per_epoch=args.iters_per_epoch,
+                          max_epochs=args.epochs, seed=args.seed,
+                          param=args.param, verbose=True)
+    with TIMERS.time("SGCP"):
+        k = sp.cpd_sgcp(t.to(dev), args.rank, args.loss, opts)
+    print(f"Final loss estimate: {min(k.loss_trace):.8e}  ({args.loss}; "
+          f"epochs: {k.nepochs}; steps kept: {k.nsteps}; failed epochs: "
+          f"{k.nfails})")
+    if not args.nowrite:
+        parent = os.path.dirname(args.stem)
+        if parent:
+            os.makedirs(parent, exist_ok=True)
+        for m, f in enumerate(k.factors):
+            _write_matrix(f"{args.stem}mode{m + 1}.mat", f)
+        with open(f"{args.stem}lambda.mat", "w") as fh:
+            for x in k.lam.cpu().tolist():
+                fh.write(f"{x:.17g}\n")
+        print(f"wrote {len(k.factors)} factor matrices and lambda.mat with "
+              f"stem {args.stem!r}")
+    print(TIMERS.report())
+    return 0
+
+
 def parse_constraints(specs, nmodes: int):
     """`--con` specs -> per-mode list of Constraint / None.
 
@@ -591,6 +628,36 @@ def main(argv=None) -> int:
                         "PATHlambda.mat (end it with / for a directory)")
     p.add_argument("--nowrite", action="store_true")
     p.set_defaults(fn=cmd_gcp)
+
+    p = sub.add_parser("sgcp",
+                       help="stochastic generalized CPD over all cells "
+                            "(unstored cells are zeros): Adam on sampled "
+                            "gradients")
+    _add_common(p)
+    p.add_argument("-r", "--rank", type=int, default=10)
+    p.add_argument("--loss", default="bernoulli-logit",
+                   choices=list(_gcp_losses))
+    p.add_argument("--param", type=float, default=None,
+                   help="loss parameter (huber: delta)")
+    p.add_argument("-e", "--epochs", type=int, default=1000,
+                   help="at most this many epochs")
+    p.add_argument("--iters-per-epoch", type=int, default=1000)
+    p.add_argument("-p", type=int, default=None, metavar="N",
+                   help="stored entries drawn per step")
+    p.add_argument("-q", type=int, default=None, metavar="N",
+                   help="cells drawn per step")
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--decay", type=float, default=0.1,
+                   help="lr multiplier after an epoch that did not improve")
+    p.add_argument("--fails", type=int, default=1,
+                   help="stop after this many + 1 such epochs")
+    p.add_argument("--seed", type=int, default=0x5EED5EED)
+    p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
+    p.add_argument("--stem", default="", metavar="PATH",
+                   help="prefix of the output files PATHmodeN.mat and "
+                        "PATHlambda.mat (end it with / for a directory)")
+    p.add_argument("--nowrite", action="store_true")
+    p.set_defaults(fn=cmd_sgcp)
 
     p = sub.add_parser("check", help="find/repair duplicates + empty slices")
     _add_common(p)

@@ -10,8 +10,9 @@ The STORED entries of the tensor are the OBSERVED entries: the objective is
 and nothing else — the convention of `complete_als`. A stored value of 0 is
 an observation of zero; cells that are not stored are unknown. For binary
 data, store the positives plus a sample of zeros (`sample_zeros`). For
-output mode m, with Omega_i the stored entries of row i and pi_x the
-Hadamard product of the other modes' factor rows at x,
+the loss over ALL cells, unstored cells counted as zeros, use `cpd_sgcp`
+(splatt_amd/sgcp.py). For output mode m, with Omega_i the stored entries of
+row i and pi_x the Hadamard product of the other modes' factor rows at x,
 
     G_m[i]  = sum_{x in Omega_i} dl/dm(val_x, mdl_x) pi_x
     frow[i] = sum_{x in Omega_i} l(val_x, mdl_x)
