@@ -319,6 +319,26 @@ int apr_fold(const double * ws, const int32_t * mrow, const int64_t * mslot,
              int32_t * done, double * B, double * Phi, int32_t * iters,
              double * viol0, void * stream);
 
+// -------------------------------------------------------- apr_pdnr.hip
+// Poisson CPD damped-Newton row solver (PDNR) of a root-sorted stream (f64),
+// rank F in 1..64, nother in 2..7, idx/mats tables of 8. One workgroup per
+// entry of `rows` (rows that have nonzeros, any order; the caller issues the
+// longest first) runs up to max_inner inner iterations of row rows[r], whose
+// nonzeros are [rowptr[row], rowptr[row + 1]) of the stream: B ([all rows,
+// F]) is updated in place, Phi receives the last pass's Phi, and iters,
+// viol0, f0, f (objective at entry and exit), mu (final damping), nback
+// (line-search evaluations) and nfail (rejected steps) one entry per row.
+// Rows not listed are not written. Returns 0 or a positive hipError_t
+// (hipErrorInvalidValue for arguments out of range or an LDS request over
+// the device limit) and never declines.
+int apr_pdnr(const int32_t * const * idx, const double * const * mats,
+             int nother, const double * vals, const int64_t * rowptr,
+             const int32_t * rows, int64_t nrows, int F, double eps_div,
+             double inner_tol, int max_inner, double mu0, double * B,
+             double * Phi, int32_t * iters, double * viol0, double * f0,
+             double * f, double * mu, int32_t * nback, int32_t * nfail,
+             void * stream);
+
 // ------------------------------------------------------------ gcp.hip
 // Generalized CPD loss-gradient pass of a root-sorted stream (f64), rank F
 // in 1..64, nother in 2..7, idx/mats tables of 8. A (the output mode's

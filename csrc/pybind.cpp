@@ -1101,6 +1101,58 @@ static void py_hip_apr_update(
   }
 }
 
+// The damped-Newton (PDNR) row solve of one mode: one launch, one workgroup
+// per entry of `rows` (the rows that have nonzeros, longest first), the
+// whole inner loop of a row inside it, no host synchronisation. rowptr has
+// one entry per row of B plus one; every output has one entry (Phi: one
+// row) per row of B and comes in zeroed.
+static void py_hip_apr_pdnr(
+    std::vector<Tensor> idx, std::vector<Tensor> mats, Tensor vals,
+    Tensor rowptr, Tensor rows, double eps_div, double inner_tol,
+    int64_t max_inner, double mu0, Tensor B, Tensor Phi, Tensor iters,
+    Tensor viol0, Tensor f0, Tensor f, Tensor mu, Tensor nback, Tensor nfail,
+    int64_t stream) {
+  const size_t nother = idx.size();
+  TORCH_CHECK(nother >= 2 && nother <= 7, "apr supports 3..8 modes");
+  TORCH_CHECK(max_inner >= 1 && max_inner <= 0x7FFFFFFF,
+              "max_inner must be >= 1");
+  TORCH_CHECK(eps_div > 0.0, "eps_div must be > 0");
+  TORCH_CHECK(mu0 > 0.0, "mu0 must be > 0");
+  const double * vp = dev_ptr<double>(vals, "vals");
+  const int64_t * rp = dev_ptr<int64_t>(rowptr, "rowptr");
+  const int32_t * rw = dev_ptr<int32_t>(rows, "rows");
+  double * bp = dev_ptr<double>(B, "B");
+  double * pp = dev_ptr<double>(Phi, "Phi");
+  int32_t * itp = dev_ptr<int32_t>(iters, "iters");
+  double * v0p = dev_ptr<double>(viol0, "viol0");
+  double * f0p = dev_ptr<double>(f0, "f0");
+  double * fp = dev_ptr<double>(f, "f");
+  double * mup = dev_ptr<double>(mu, "mu");
+  int32_t * nbp = dev_ptr<int32_t>(nback, "nback");
+  int32_t * nfp = dev_ptr<int32_t>(nfail, "nfail");
+  TORCH_CHECK(B.dim() == 2, "B must be [rows, rank]");
+  const int64_t nrows = B.size(0);
+  const int F = (int)B.size(1);
+  TORCH_CHECK(F >= 1 && F <= 64, "apr supports rank 1..64, got ", F);
+  TORCH_CHECK(Phi.dim() == 2 && Phi.size(0) == nrows && Phi.size(1) == F,
+              "Phi must have the shape of B");
+  TORCH_CHECK(iters.numel() == nrows && viol0.numel() == nrows
+              && f0.numel() == nrows && f.numel() == nrows
+              && mu.numel() == nrows && nback.numel() == nrows
+              && nfail.numel() == nrows,
+              "iters, viol0, f0, f, mu, nback and nfail need one entry per "
+              "row of B");
+  TORCH_CHECK(rowptr.numel() == nrows + 1,
+              "rowptr needs one entry per row of B plus one");
+  TORCH_CHECK(rows.numel() <= nrows, "more listed rows than rows of B");
+  auto ip = stream_table(idx, nother, vals.numel());
+  auto mp = factor_table<double>(mats, nother, F);
+  check_rc(gpu::apr_pdnr(ip.data(), mp.data(), (int)nother, vp, rp, rw,
+                         rows.numel(), F, eps_div, inner_tol, (int)max_inner,
+                         mu0, bp, pp, itp, v0p, f0p, fp, mup, nbp, nfp,
+                         (void *)stream), "apr pdnr");
+}
+
 // ------------------------------------- generalized CPD / GCP (f64 only)
 
 // The loss-gradient pass of one mode: G[i] = sum dl/dm(val, mdl) pi over the
@@ -1341,6 +1393,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused block-ADMM factor update (in place on H, U)");
   m.def("hip_apr_update", &py_hip_apr_update,
         "CP-APR multiplicative row update of a root-sorted stream (f64)");
+  m.def("hip_apr_pdnr", &py_hip_apr_pdnr,
+        "CP-APR damped-Newton (PDNR) row solve of a root-sorted stream (f64)");
   m.def("hip_gcp_grad", &py_hip_gcp_grad,
         "GCP loss-gradient pass of a root-sorted stream (f64)");
   m.def("hip_sgcp_grad", &py_hip_sgcp_grad,

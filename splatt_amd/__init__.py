@@ -23,7 +23,8 @@ from splatt_amd.admm import (AoAdmmOptions, Constraint, ConstrainedKruskal,
                              admm_solve, admm_update, box, cpd_aoadmm, l1,
                              nonneg, nonneg_l1)
 from splatt_amd.tucker import Tucker, TuckerOptions, ttmc, tucker_hooi
-from splatt_amd.apr import AprOptions, PoissonKruskal, apr_update, cpd_apr
+from splatt_amd.apr import (AprOptions, PoissonKruskal, apr_update,
+                            apr_update_pdnr, cpd_apr)
 from splatt_amd.gcp import (GcpKruskal, GcpOptions, cpd_gcp, gcp_fg, gcp_grad,
                             sample_zeros)
 from splatt_amd.sgcp import (GcpSample, SgcpKruskal, SgcpOptions, adam_step,
@@ -43,7 +44,8 @@ __all__ = [
     "AoAdmmOptions", "Constraint", "ConstrainedKruskal", "admm_solve",
     "admm_update", "cpd_aoadmm", "nonneg", "l1", "nonneg_l1", "box",
     "Tucker", "TuckerOptions", "ttmc", "tucker_hooi",
-    "AprOptions", "PoissonKruskal", "apr_update", "cpd_apr",
+    "AprOptions", "PoissonKruskal", "apr_update", "apr_update_pdnr",
+    "cpd_apr",
     "GcpOptions", "GcpKruskal", "gcp_grad", "gcp_fg", "cpd_gcp",
     "sample_zeros",
     "GcpSample", "SgcpOptions", "SgcpKruskal", "gcp_sample", "gcp_sgrad",

@@ -135,7 +135,8 @@ def cmd_apr(args) -> int:
     if dev == "auto":
         dev = "cuda" if torch.cuda.is_available() else "cpu"
     opts = sp.AprOptions(max_iters=args.its, max_inner=args.inner,
-                         tolerance=args.tol, seed=args.seed, verbose=True)
+                         tolerance=args.tol, seed=args.seed, verbose=True,
+                         method=args.alg)
     with TIMERS.time("APR"):
         cs = sp.csf_alloc(t.to(dev), "all")
         print(stats_csf(cs))
@@ -144,6 +145,8 @@ def cmd_apr(args) -> int:
           f"{k.kkt_trace[-1]:.3e}  (iterations: {k.niters}; inner "
           f"iterations: {sum(k.inner_trace)}; "
           f"{'converged' if k.converged else 'not converged'})")
+    if args.alg == "pdnr":
+        print(f"Line-search evaluations: {sum(k.nback_trace)}")
     if not args.nowrite:
         parent = os.path.dirname(args.stem)
         if parent:
@@ -595,7 +598,10 @@ def main(argv=None) -> int:
                    help="KKT tolerance, outer and per row (0: run every "
                         "iteration)")
     p.add_argument("--inner", type=int, default=10,
-                   help="multiplicative updates per row and mode update")
+                   help="inner iterations per row and mode update")
+    p.add_argument("--alg", default="mu", choices=["mu", "pdnr"],
+                   help="row solver: multiplicative updates (mu) or the "
+                        "damped-Newton solver (pdnr)")
     p.add_argument("--seed", type=int, default=0x5EED5EED)
     p.add_argument("--device", default="auto", choices=["auto", "cpu", "cuda"])
     p.add_argument("--stem", default="", metavar="PATH",
